@@ -21,11 +21,17 @@ A step (--scaling):
 With --gpus N the driver starts one process per GPU (torch.distributed.run);
 the only cross-rank traffic is the barrier and the max-over-ranks time.
 
-Also reported: buildRouteDb("1") ms (cold: right after a topology-changing
-adjacency update, so it includes the device mirror patch and the SPF; warm:
-memoized SPF), the dominant kernels' HBM roofline figures, and the CPU oracle
-(a port of the reference algorithm with its data structures) timed on a
-bounded sample of the same workload on this host.
+A plain run sets up, warms up, times the --steps steps and prints the result
+line (metric, value, unit, ms_per_step, ...). --dump-outputs DIR also writes a
+seeded sample of what the last timed step left on the device (dump_outputs).
+
+With --full also checked and reported: the timed output against the grid's
+closed-form distances, buildRouteDb("1") ms (cold: right after a
+topology-changing adjacency update, so it includes the device mirror patch and
+the SPF; warm: memoized SPF), the dominant kernels' HBM roofline figures, the
+other BASELINE configs (--legs), and the CPU oracle (a port of the reference
+algorithm with its data structures) timed on a bounded sample of the same
+workload on this host.
 """
 import argparse
 import json
@@ -57,6 +63,13 @@ def parse():
     p.add_argument("--lanes", type=int, default=2,
                    help="stream lanes per rank: a rank's what-if variants are dealt over this many "
                         "contexts (own HIP stream each) so their sweeps overlap on the GPU")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: the distance check, the sweep "
+                        "probe and roofline, buildRouteDb timings, the CPU baseline and the legs "
+                        "(--no-route-db, --no-cpu-baseline and --legs trim a full run)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write a seeded sample of the last step's dist and "
+                        "first-hop rows to DIR/<name>.npy (float64)")
     p.add_argument("--cpu-sample", type=int, default=256, help="oracle sources per thread config")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="oracle threads (0: every CPU this process may use)")
@@ -67,7 +80,10 @@ def parse():
     p.add_argument("--no-route-db", action="store_true")
     p.add_argument("--legs", default="c1,c2w,c3,c4,c5",
                    help="extra BASELINE configs reported under 'legs' (c1,c2w,c3,c4,c5; '' for none)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def drain_what_if_link(adj_dbs, n, rank):
@@ -160,7 +176,7 @@ def main():
     def run_all():
         for _, _, _, sw in sweeps:
             if sw is not None:
-                sw.run()  # asynchronous on the context stream
+                launch(sw)
 
     def sync_all():
         for _, _, _, sw in sweeps:
@@ -181,15 +197,22 @@ def main():
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
 
+    value = total_units * args.steps / elapsed
+    ms_per_step = elapsed * 1e3 / args.steps
+
+    # the last timed step's rows, before anything else runs on the contexts
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sweeps, rank, world)
+
     # device time of one sweep's launches (HIP events on the sweep's own
     # stream), measured outside the timed region
     probe = next((sw for _, srcs, _, sw in sweeps if sw is not None and len(srcs) == n * n),
                  next((sw for *_, sw in sweeps if sw is not None), None))
     kernel_ms, phases = [], []
     step_plan = None
-    if probe is not None:
+    if args.full and probe is not None:
         for _ in range(max(3, min(args.steps, 10))):
-            probe.run()
+            launch(probe)
             kernel_ms.append(probe.last_ms())
             phases.append(probe.phase_ms())
         probe_info = probe.info()
@@ -199,7 +222,7 @@ def main():
         try:
             sp_ms, sp_ph = [], []
             for _ in range(max(3, min(args.steps, 10))):
-                probe.run()
+                launch(probe)
                 sp_ms.append(probe.last_ms())
                 sp_ph.append(probe.phase_ms())
             step_plan = (statistics.mean(sp_ms), [round(statistics.mean(p[i] for p in sp_ph), 4) for i in (0, 1)],
@@ -207,29 +230,14 @@ def main():
         finally:
             del os.environ["ORH_MS_BLOCK"]
 
-    value = total_units * args.steps / elapsed
-    ms_per_step = elapsed * 1e3 / args.steps
-
-    # size-independent correctness check on the timed output: unit metrics,
-    # so dist(src, v) is the Manhattan distance on the undrained grid
-    import numpy as np
-    rr, cc = np.divmod(np.arange(n * n), n)
-    for t, srcs, ls, sw in sweeps:
-        if t != 0 or sw is None:
-            continue
-        node_ids = {name: i for i, name in enumerate(ls._impl.node_names())}
-        ids = np.array([node_ids[str(v)] for v in range(n * n)])
-        for i in (0, len(srcs) // 2, len(srcs) - 1):
-            s_ = int(srcs[i])
-            dist_row, _ = sw.fetch(i)
-            if not np.array_equal(dist_row[ids], np.abs(rr - rr[s_]) + np.abs(cc - cc[s_])):
-                raise SystemExit(f"bench: wrong distances for source {s_}")
+    if args.full:
+        check_distances(sweeps, n)
 
     # N ranks: rank r runs block r of the C3 prefix-sharded route build and
     # of the C4 what-if job / KSP2 batch on its own GPU (bench_legs.run_ranks);
     # rank 0 reports the max over ranks. Untimed by the step's clock.
     rank_legs = None
-    if world > 1 and args.legs:
+    if args.full and world > 1 and args.legs:
         import bench_legs
         mine = bench_legs.run_ranks(args.legs.split(","), hip, rank, world)
         gathered = [None] * world
@@ -240,8 +248,15 @@ def main():
         barrier()
         return
 
+    N, E = probe.nodes, probe.edges
+    out = result_line(args, world, value, ms_per_step, N, E, total_units)
+    if not args.full:  # the headline figure alone
+        print(json.dumps(out), flush=True)
+        barrier()
+        return
+
     # roofline of the sweep: B = 4(N+1) + 8E + N(4D + 4W)
-    N, E, W = probe.nodes, probe.edges, probe.words
+    W = probe.words
     srcs_probe = probe.sources
     bytes_per_source = 4 * (N + 1) + 8 * E + N * (4 * 1 + 4 * W)
     per_launch = bytes_per_source * srcs_probe
@@ -250,55 +265,34 @@ def main():
     out_bytes = srcs_probe * N * (4 + 4 * W)  # the dist + first-hop rows alone
 
     traffic, traffic_src = pmc_traffic()
-    parallelism = {"whatif": f"{args.topologies} what-if variants split over {world} rank(s)",
-                   "strong": f"one topology, sources in {world} degree-weighted block(s)",
-                   "weak": f"{world} variant(s), one per rank"}[args.scaling]
-    out = {
-        "metric": "all-source SPF runs/sec + buildRouteDb ms on 10k-node topology",
-        "value": round(value, 1),
-        "unit": "SPF-sources/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak" if args.scaling == "weak" else "strong",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic: reference benchmark grid generator (createGrid n=100)",
-        "config": {"workload": f"C2 {n}x{n} grid all-sources SPF (N={N}, E={E})",
-                   "step": (f"{args.topologies} x {n * n} sources" if args.scaling == "whatif"
-                            else f"{total_units} sources"),
-                   "parallelism": parallelism},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel_ms": round(kms, 4),
-                     # the sweep ran alone: the lone-sweep plan (12-wave
-                     # batches); the step's overlapping sweeps run 8-wave ones
-                     "plan": {"ms_threads": probe_info.get("ms_threads"),
-                              "batch_sources": probe_info.get("batch_sources")},
-                     "phase_ms": [round(statistics.mean(p[0] for p in phases), 4),
-                                  round(statistics.mean(p[1] for p in phases), 4)],
-                     # the probe above runs the lone-sweep plan (nothing else in
-                     # flight); the step's sweeps run this one
-                     "step_plan_sweep": None if step_plan is None else {
-                         "kernel_ms": round(step_plan[0], 4), "phase_ms": step_plan[1],
-                         "ms_threads": step_plan[2].get("ms_threads"),
-                         "achieved": round(per_launch / (step_plan[0] * 1e-3) / 1e9, 1),
-                         "frac": round(per_launch / (step_plan[0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-                     "algorithmic_bytes_per_source": bytes_per_source,
-                     "sources_per_launch": srcs_probe,
-                     "output_floor": {"bytes": out_bytes,
-                                      "frac": round(out_bytes / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-                     # the timed region as a whole: every sweep's algorithmic
-                     # bytes over the wall time of a step (overlapping lanes)
-                     "step": {"achieved": round(bytes_per_source * total_units / world / (ms_per_step * 1e-3) / 1e9, 1),
-                              "frac": round(bytes_per_source * total_units / world / (ms_per_step * 1e-3) / 1e9
-                                            / HBM_PEAK_GBS, 4),
-                              "note": "per-GPU algorithmic bytes of one step / ms_per_step; 'achieved' above "
-                                      "is one sweep launch alone (HIP events), as rocprof's kernel averages"}},
-    }
+    step_gbs = bytes_per_source * total_units / world / (ms_per_step * 1e-3) / 1e9
+    out["roofline"] = {
+        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "traffic": traffic, "traffic_source": traffic_src,
+        "kernel_ms": round(kms, 4),
+        # the sweep ran alone: the lone-sweep plan (12-wave
+        # batches); the step's overlapping sweeps run 8-wave ones
+        "plan": {"ms_threads": probe_info.get("ms_threads"),
+                 "batch_sources": probe_info.get("batch_sources")},
+        "phase_ms": [round(statistics.mean(p[0] for p in phases), 4),
+                     round(statistics.mean(p[1] for p in phases), 4)],
+        # the probe above runs the lone-sweep plan (nothing else in
+        # flight); the step's sweeps run this one
+        "step_plan_sweep": None if step_plan is None else {
+            "kernel_ms": round(step_plan[0], 4), "phase_ms": step_plan[1],
+            "ms_threads": step_plan[2].get("ms_threads"),
+            "achieved": round(per_launch / (step_plan[0] * 1e-3) / 1e9, 1),
+            "frac": round(per_launch / (step_plan[0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+        "algorithmic_bytes_per_source": bytes_per_source,
+        "sources_per_launch": srcs_probe,
+        "output_floor": {"bytes": out_bytes,
+                         "frac": round(out_bytes / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+        # the timed region as a whole: every sweep's algorithmic
+        # bytes over the wall time of a step (overlapping lanes)
+        "step": {"achieved": round(step_gbs, 1), "frac": round(step_gbs / HBM_PEAK_GBS, 4),
+                 "note": "per-GPU algorithmic bytes of one step / ms_per_step; 'achieved' above "
+                         "is one sweep launch alone (HIP events), as rocprof's kernel averages"}}
 
     if not args.no_route_db and base is not None:
         adj_dbs, prefixes, als, ps, ls = base
@@ -350,6 +344,110 @@ def main():
 
     print(json.dumps(out), flush=True)
     barrier()
+
+
+def launch(sw):
+    """One sweep's launches, asynchronous on its context's stream; every run
+    of a sweep, timed or not, goes through here."""
+    sw.run()
+
+
+def check_distances(sweeps, n):
+    """Size-independent correctness check on the timed output: unit metrics,
+    so dist(src, v) is the Manhattan distance on the undrained grid."""
+    import numpy as np
+    rr, cc = np.divmod(np.arange(n * n), n)
+    for t, srcs, ls, sw in sweeps:
+        if t != 0 or sw is None:
+            continue
+        node_ids = {name: i for i, name in enumerate(ls._impl.node_names())}
+        ids = np.array([node_ids[str(v)] for v in range(n * n)])
+        for i in (0, len(srcs) // 2, len(srcs) - 1):
+            s_ = int(srcs[i])
+            dist_row, _ = sw.fetch(i)
+            if not np.array_equal(dist_row[ids], np.abs(rr - rr[s_]) + np.abs(cc - cc[s_])):
+                raise SystemExit(f"bench: wrong distances for source {s_}")
+
+
+def result_line(args, world, value, ms_per_step, N, E, total_units):
+    """The result line of a plain run: the headline figure and what describes
+    the run. --full adds its measurements to this dict."""
+    n = args.grid
+    parallelism = {"whatif": f"{args.topologies} what-if variants split over {world} rank(s)",
+                   "strong": f"one topology, sources in {world} degree-weighted block(s)",
+                   "weak": f"{world} variant(s), one per rank"}[args.scaling]
+    return {
+        "metric": "all-source SPF runs/sec + buildRouteDb ms on 10k-node topology",
+        "value": round(value, 1),
+        "unit": "SPF-sources/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak" if args.scaling == "weak" else "strong",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic: reference benchmark grid generator (createGrid n=100)",
+        "config": {"workload": f"C2 {n}x{n} grid all-sources SPF (N={N}, E={E})",
+                   "step": (f"{args.topologies} x {n * n} sources" if args.scaling == "whatif"
+                            else f"{total_units} sources"),
+                   "parallelism": parallelism},
+    }
+
+
+DUMP_BYTES = 48 << 20  # all ranks' arrays together (64 MB is the limit; leaves room for the file headers)
+DUMP_SEED = 7001
+
+
+def dump_outputs(out_dir, sweeps, rank, world):
+    """What the timed path left on the device after its last step, as a
+    caller of the sweeps receives it (SpfSweep.fetch): per sweep a seeded
+    sample of its sources' rows, nodes in name order, written as float64
+    (exact for u32) to
+      sources_v<variant>.npy     [K]        the sampled sources' node names
+      dist_v<variant>.npy        [K][N]     u32 distance rows
+      first_hops_v<variant>.npy  [K][N][W]  u32 ECMP first-hop mask words
+    (N ranks: ..._r<rank>.npy). All files together stay under DUMP_BYTES: a
+    sweep whose share holds less than one whole row keeps one source and a
+    seeded sample of M < N nodes, listed (positions in name order) in
+      nodes_v<variant>.npy       [M]
+    and where even that is too much for every sweep, only the first sweeps
+    are written. The sample depends on the arguments alone, so two builds run
+    with the same arguments write comparable files."""
+    import random
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    live = [(t, srcs, ls, sw) for t, srcs, ls, sw in sweeps if sw is not None]
+    if not live:
+        return
+    budget = DUMP_BYTES // max(1, world)
+    # one source entry, one node's dist + mask words, its nodes_v entry
+    smallest = max(8 * (3 + sw.words) for *_, sw in live)
+    live = live[:max(1, budget // smallest)]
+    share = budget // len(live)
+    tag = f"_r{rank}" if world > 1 else ""
+    for t, srcs, ls, sw in live:
+        names = ls._impl.node_names()
+        order = np.argsort(np.array([int(v) for v in names]), kind="stable")  # name order
+        rng = random.Random(DUMP_SEED + t)
+        row_bytes = 8 + 8 * sw.nodes * (1 + sw.words)
+        picks = sorted(rng.sample(range(len(srcs)), min(max(1, share // row_bytes), len(srcs))))
+        if share < row_bytes:
+            keep = max(1, min(sw.nodes, (share - 8) // (8 * (2 + sw.words))))
+            nodes = np.array(sorted(rng.sample(range(sw.nodes), keep)))
+            np.save(os.path.join(out_dir, f"nodes_v{t:03d}{tag}.npy"), nodes.astype(np.float64))
+            order = order[nodes]
+        dist = np.empty((len(picks), len(order)), dtype=np.float64)
+        hops = np.empty((len(picks), len(order), sw.words), dtype=np.float64)
+        for k, i in enumerate(picks):
+            d, nh = sw.fetch(i)
+            dist[k] = d[order]
+            hops[k] = nh.reshape(sw.nodes, sw.words)[order]
+        np.save(os.path.join(out_dir, f"sources_v{t:03d}{tag}.npy"),
+                np.array([float(srcs[i]) for i in picks], dtype=np.float64))
+        np.save(os.path.join(out_dir, f"dist_v{t:03d}{tag}.npy"), dist)
+        np.save(os.path.join(out_dir, f"first_hops_v{t:03d}{tag}.npy"), hops)
 
 
 # newest committed PMC summary of this command (tools/profile.sh +

@@ -6,7 +6,7 @@
 set -e
 TAG=${1:-run}
 shift || true
-ARGS=${@:---steps 10 --warmup 2 --no-cpu-baseline --no-route-db --legs=}
+ARGS=${@:---full --steps 10 --warmup 2 --no-cpu-baseline --no-route-db --legs=}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
