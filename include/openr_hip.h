@@ -172,6 +172,8 @@ int orh_set_repair_mode(orh_ctx* ctx, int mode);
                                    first hops fused, one workgroup per source */
 #define ORH_VARIANT_WMS 13      /* general metrics, many sources: 4-source Bellman-Ford
                                    batches in LDS, then the first-hop phase */
+#define ORH_VARIANT_WMS_SLICED 14 /* the same for graphs with nodes of any degree: the in-links
+                                     in a sliced-ELL layout in global memory */
 typedef struct orh_spf_info {
   int32_t variant;     /* ORH_VARIANT_* of the distance phase */
   uint32_t rows;       /* distance rows searched (sources + neighbour rows) */
@@ -179,11 +181,14 @@ typedef struct orh_spf_info {
   uint32_t hop_nodes;  /* first-hop phase: nodes per thread over u8 level rows
                           (16 or 4), 1 for the u32-row kernel, 0 when fused */
   uint32_t hop_split;  /* first-hop phase: workgroups per source */
-  uint32_t batch_sources; /* MS-BFS: sources per workgroup (<= mask_bits), else 0 */
-  uint32_t ms_threads;    /* MS-BFS: threads per workgroup (1024: the latency plan), else 0 */
+  uint32_t batch_sources; /* MS-BFS, sliced WMS: sources per workgroup (<= mask_bits), else 0 */
+  uint32_t ms_threads;    /* MS-BFS: threads per workgroup (1024: the latency plan); sliced WMS:
+                             threads per batch; else 0 */
   uint32_t ms_skip;       /* MS-BFS: interval skip on (latency plan or ORH_MS_SKIP=1) */
   uint32_t ms_direct;     /* MS-BFS / WMS: the node layout kept the host order (MS-BFS: rows
                              written by the search kernel, no finalize pass) */
+  uint32_t wsl_links;     /* sliced WMS: live in-links of the layout, else 0 */
+  uint32_t wsl_slots;     /* sliced WMS: slot words of the layout, padding included, else 0 */
 } orh_spf_info;
 int orh_last_spf_info(const orh_ctx* ctx, orh_spf_info* out);
 /* device time (HIP events on the context stream) of the last orh_spf_run;

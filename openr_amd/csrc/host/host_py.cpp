@@ -449,6 +449,8 @@ class SpfSweep {
     d["ms_threads"] = i.ms_threads;
     d["ms_skip"] = i.ms_skip;
     d["ms_direct"] = i.ms_direct;
+    d["wsl_links"] = i.wsl_links;
+    d["wsl_slots"] = i.wsl_slots;
     return d;
   }
   py::tuple fetch(size_t i) {

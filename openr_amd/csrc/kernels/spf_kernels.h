@@ -81,6 +81,15 @@ struct SpfArgs {
   // forward then backward (else chunk j of wave w is j * waves + w, one pass)
   uint32_t wms_band;
   uint32_t recs_k;  // ELL width of `recs` (kernels launched from plans that do not know it)
+  // sliced multi-source Bellman-Ford (kWmsSliced): the same slot words in a
+  // sliced-ELL layout over the Cuthill-McKee ids - slice s (nodes [64 s, 64 s
+  // + 64)) holds columns of 64 words from wsl_off[s] to wsl_off[s + 1] (a
+  // multiple of 4 columns); wave w owns slices [wsl_band[w], wsl_band[w + 1]);
+  // wsl_ovl: some slot carries the overloaded flag
+  const uint32_t* wsl_slots;
+  const uint32_t* wsl_off;   // [slices + 1]
+  const uint32_t* wsl_band;  // [waves + 1]
+  uint32_t wsl_ovl;
 };
 
 // phase 2: first-hop masks of the requested rows from the distance rows of
@@ -126,7 +135,8 @@ enum class SpfVariant {
   kBfsNh,     // uniform metric, few sources: BFS with the first hops fused (no phase 2)
   kRepair,    // ignore-set batch derived from its sources' plain SPFs (whatif_kernels.hip)
   kLdsNh,     // general metrics, labels {dist, first hops} in LDS, first hops fused (no phase 2)
-  kWms        // general metrics, many sources: 4-source Bellman-Ford in LDS, then phase 2
+  kWms,       // general metrics, many sources: 4-source Bellman-Ford in LDS, then phase 2
+  kWmsSliced  // the same for any node degree: in-links in a sliced-ELL layout in global memory
 };
 // spf_wms_kernel: LDS bytes of one batch of `sources` (4 or 8) sources
 // (u16 x sources per node + 1), and the batch width launch_spf_wms takes
@@ -138,6 +148,14 @@ uint32_t wms_sources(uint32_t n_nodes, size_t lds_limit);
 // wms_k: in-link slots per node of a.wms_slots (4 or 8); a.recs_k: the ELL
 // width of a.recs (for the u64 LDS search of the flagged rows)
 hipError_t launch_spf_wms(SpfArgs a, uint32_t n_rows, uint32_t wms_k, size_t lds_limit, hipStream_t s);
+struct SpfPlan;
+// spf_wms_sliced_kernel: batches of wms_sources rows, `block` threads (256,
+// 512 or 1,024: a.wsl_band holds block / 64 bands); rows whose labels come
+// too close to 16 bits are listed in a.ovf_rows (n_rows + 1 words) and redone
+// by `redo`, the two-phase plan (kDist16 / kDist32) the sweep would run
+// otherwise, whose LDS must fit. Writes dist rows only.
+hipError_t launch_spf_wms_sliced(const SpfPlan& redo, SpfArgs a, uint32_t n_rows, uint32_t block,
+                                 size_t lds_limit, hipStream_t s);
 // spf_lds_nh_kernel: LDS bytes per search (packed: u32 labels, <= 16
 // distinct neighbours per source; else u64 labels)
 size_t lds_nh_bytes(uint32_t n_nodes, bool packed);

@@ -1124,7 +1124,11 @@ __global__ __launch_bounds__(kMaxBlock) void spf_dist_kernel(SpfArgs a) {
   __shared__ uint32_t s_min[3];
   const uint32_t N = a.n_nodes;
   const uint32_t NB = (N + 31) >> 5;
-  const uint32_t tid = threadIdx.x, nthr = blockDim.x, row = blockIdx.x;
+  const uint32_t tid = threadIdx.x, nthr = blockDim.x;
+  // a.row_list (nullable): workgroup b searches row row_list[b] while b <
+  // *row_count, else exits (the rows launch_spf_wms_sliced's batches flagged)
+  if (a.row_list && blockIdx.x >= *a.row_count) return;
+  const uint32_t row = a.row_list ? a.row_list[blockIdx.x] : blockIdx.x;
   uint32_t* dist = lds;
   uint32_t* pend = lds + a.lds_pend_off / 4;
   const Src s(a, row);
@@ -2472,6 +2476,141 @@ __global__ __launch_bounds__(1024) ORH_WMS_ATTR void spf_wms_kernel(SpfArgs a) {
   }
 }
 
+// The same search with the in-links in global memory instead of registers,
+// for graphs with nodes of any degree (kWmsSliced). Sliced ELL over the
+// Cuthill-McKee ids: slice s is the 64 nodes [64 s, 64 s + 64), one lane per
+// node, and as wide as its largest in-degree (rounded up to 4 columns);
+// column k of slice s is the 64 words a.wsl_slots[a.wsl_off[s] + 64 k ..], one
+// coalesced 256-byte load per wave. A slot is the spf_wms_kernel word {u | w(u
+// -> v) << 16 | overloaded(u) << 31}, u = N for padding and down links. A node
+// is owned by one lane, so no two lanes ever write the same label. Wave w
+// owns the slices [a.wsl_band[w], a.wsl_band[w + 1]) (cut by the host so the
+// waves carry like column counts) and sweeps them forward, then backward,
+// each round. The slots are shared by every batch and read-only, so a slot
+// whose u is overloaded is masked to u = N as it is read in the rounds.
+template <int S>
+__global__ __launch_bounds__(1024) void spf_wms_sliced_kernel(SpfArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  constexpr uint32_t W = S / 2;  // dwords per node
+  typedef uint32_t DV __attribute__((ext_vector_type(W)));
+  const uint32_t N = a.n_nodes;
+  const uint32_t tid = threadIdx.x, B = blockDim.x;
+  const uint32_t b0 = blockIdx.x * S;
+  const uint32_t nsrc = min(static_cast<uint32_t>(S), a.n_rows - b0);
+  __shared__ uint32_t s_prog[3], s_ovf;
+  DV* D = reinterpret_cast<DV*>(lds);  // [N + 1]; D[N] stays unreached
+  {
+    DV none;
+#pragma unroll
+    for (uint32_t q = 0; q < W; ++q) none[q] = ~0u;
+    for (uint32_t i = tid; i <= N; i += B) D[i] = none;
+  }
+  if (tid < 3) s_prog[tid] = 0u;
+  if (tid == 0) s_ovf = 0u;
+  __syncthreads();
+  if (tid < nsrc) {  // sources may repeat: clear each lane's half alone
+    const uint32_t src = a.dev_of[a.srcs[a.order[b0 + tid]]];
+    atomicAnd(reinterpret_cast<uint32_t*>(D + src) + (tid >> 1), (tid & 1u) ? 0x0000FFFFu : 0xFFFF0000u);
+  }
+  __syncthreads();
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t lane = tid & 63u;
+  const uint32_t sb = a.wsl_band[wave], se = a.wsl_band[wave + 1];
+  const uint32_t* slots = a.wsl_slots + lane;
+  // an overloaded source reaches its neighbours and no further (as in
+  // spf_wms_kernel): a flagged slot contributes w to the lanes where u is the
+  // source (label 0: only a source holds it, and this pass writes nothing
+  // below 1), once, here. a.wsl_ovl = 0: the layout has no flagged slot
+  if (a.wsl_ovl) {
+    for (uint32_t s = sb; s < se; ++s) {
+      const uint32_t o1 = a.wsl_off[s + 1];
+      const uint32_t v = min(s * 64u + lane, N);
+      for (uint32_t o = a.wsl_off[s]; o < o1; o += 64u) {
+        const uint32_t sl = slots[o];
+        if (!(sl & kWmsOvl)) continue;
+        const uint32_t u = sl & 0xFFFFu, w = (sl >> 16) & 0x7FFFu;
+        const DV du = D[u];
+        DV d = D[v];  // v < N: a slot of a padding node is never flagged
+#pragma unroll
+        for (uint32_t q = 0; q < W; ++q) {
+          const uint32_t lo = (du[q] & 0xFFFFu) == 0u ? w : 0xFFFFu, hi = (du[q] >> 16) == 0u ? w : 0xFFFFu;
+          d[q] = pk_min_u16(d[q], lo | (hi << 16));
+        }
+        D[v] = d;
+      }
+    }
+    __syncthreads();
+  }
+  for (uint32_t round = 1;; ++round) {
+    int prog = 0;
+    auto relax = [&](uint32_t s) {
+      const uint32_t o1 = a.wsl_off[s + 1];
+      const uint32_t v = min(s * 64u + lane, N);  // a lane past N: every slot N, never changes
+      const DV own = D[v];
+      DV acc = own;
+      // 4 columns at a time (a slice's width is a multiple of 4): the slot
+      // loads, then the label reads, in flight together
+#pragma unroll 2
+      for (uint32_t o = a.wsl_off[s]; o < o1; o += 256u) {
+        uint32_t sl[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sl[k] = slots[o + 64u * k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sl[k] = (sl[k] & kWmsOvl) ? N : sl[k];  // dead after the pass above
+        DV du[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) du[k] = D[sl[k] & 0xFFFFu];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          // {w, w}: the high half twice (padding: w = 0 on the unreached entry)
+          const uint32_t wr = __builtin_amdgcn_perm(sl[k], sl[k], 0x03020302u);
+#pragma unroll
+          for (uint32_t q = 0; q < W; ++q) acc[q] = pk_min_u16(acc[q], pk_add_sat_u16(du[k][q], wr));
+        }
+      }
+      bool changed = false;
+#pragma unroll
+      for (uint32_t q = 0; q < W; ++q) changed |= acc[q] != own[q];
+      if (changed) {
+        D[v] = acc;
+        prog = 1;
+      }
+    };
+    // forward, then back (the last slice was relaxed just now): a band passes
+    // its changes both ways in one round
+    for (uint32_t s = sb; s < se; ++s) relax(s);
+    if (se > sb)
+      for (uint32_t s = se - 1; s-- > sb;) relax(s);
+    if (prog) s_prog[round % 3u] = 1u;
+    lds_barrier();
+    if (!s_prog[round % 3u]) break;
+    if (tid == 0) s_prog[(round + 2u) % 3u] = 0u;
+  }
+  // rows out in host order, as spf_wms_kernel writes them
+  const uint32_t lim = a.wms_limit;
+  uint32_t* out[S];
+#pragma unroll
+  for (uint32_t k = 0; k < S; ++k)
+    out[k] = k < nsrc ? dist_row(a.out_dist, a.scratch, a.n_out, N, a.order[b0 + k]) : nullptr;
+  bool ovf = false;
+  for (uint32_t i = tid; i < N; i += B) {
+    const DV d = D[a.dev_of[i]];
+#pragma unroll
+    for (uint32_t k = 0; k < S; ++k) {
+      if (k >= nsrc) break;
+      const uint32_t l = (d[k / 2] >> ((k & 1u) * 16u)) & 0xFFFFu;
+      ovf |= l != 0xFFFFu && l > lim;
+      __builtin_nontemporal_store(l == 0xFFFFu ? kInf : l, &out[k][i]);
+    }
+  }
+  if (ovf) s_ovf = 1u;
+  __syncthreads();
+  if (s_ovf && tid < nsrc) {
+    const uint32_t k = atomicAdd(&a.ovf_rows[0], 1u);
+    a.ovf_rows[1 + k] = a.order[b0 + tid];
+  }
+}
+
 size_t wms_lds_bytes(uint32_t n_nodes, uint32_t sources) {
   const size_t cw = (static_cast<size_t>(n_nodes) + 63) / 64 / 32 + 1;
   return (static_cast<size_t>(n_nodes) + 1) * 2 * sources + 3 * cw * 4;  // labels, then the chunk-change bitmaps
@@ -3513,6 +3652,32 @@ hipError_t launch_spf_wms(SpfArgs a, uint32_t n_rows, uint32_t wms_k, size_t lds
   const size_t lds64 = lds_nh_bytes(a.n_nodes, false);
   return a.recs_k == 8 ? launch(spf_lds_nh_kernel<8, false>, a, n_rows, 256, lds64, s)
                        : launch(spf_lds_nh_kernel<4, false>, a, n_rows, 256, lds64, s);
+}
+
+hipError_t launch_spf_wms_sliced(const SpfPlan& redo, SpfArgs a, uint32_t n_rows, uint32_t block,
+                                 size_t lds_limit, hipStream_t s) {
+  if (n_rows == 0) return hipSuccess;
+  if (!a.ovf_rows || !a.wsl_slots || !a.wsl_off || !a.wsl_band || a.n_nodes > 20480 ||
+      (block != 256 && block != 512 && block != 1024) ||
+      (redo.variant != SpfVariant::kDist16 && redo.variant != SpfVariant::kDist32))
+    return hipErrorInvalidValue;
+  a.n_rows = n_rows;
+  a.row_list = nullptr;
+  a.row_count = nullptr;
+  hipError_t e = hipMemsetAsync(a.ovf_rows, 0, 4, s);
+  if (e != hipSuccess) return e;
+  const uint32_t S = wms_sources(a.n_nodes, lds_limit);
+  const uint32_t batches = (n_rows + S - 1) / S;
+  const size_t lds = wms_lds_bytes(a.n_nodes, S);
+  e = S == 8 ? launch(spf_wms_sliced_kernel<8>, a, batches, block, lds, s)
+             : launch(spf_wms_sliced_kernel<4>, a, batches, block, lds, s);
+  if (e != hipSuccess) return e;
+  // rows whose distances may not fit 16 bits: the two-phase plan's own search
+  // (distances only, any neighbour count) over the list; workgroups past its
+  // length exit at once
+  a.row_list = a.ovf_rows + 1;
+  a.row_count = a.ovf_rows;
+  return launch_spf(redo, a, n_rows, s);
 }
 
 hipError_t launch_spf(const SpfPlan& plan, SpfArgs a, uint32_t n_rows, hipStream_t s) {

@@ -137,6 +137,16 @@ struct orh_graph {
   uint32_t* d_wms = nullptr;
   bool wms_dirty = true, wms_ok = false;
   uint32_t wms_maxw = 0, wms_k = 4;
+  // sliced multi-source Bellman-Ford (kWmsSliced): the same slot words for
+  // any degree, column-major per 64-node slice (sync_wms_sliced_layout).
+  // d_wsl: slots | slice offsets [slices + 1] | band starts for 4, 8 and 16
+  // waves (5 + 9 + 17 words); wsl_ok: N <= 20,480 and live metrics 1..0x7FFF
+  uint32_t* d_wsl = nullptr;
+  size_t d_wsl_cap = 0;  // in u32
+  bool wsl_dirty = true, wsl_ok = false, wsl_ovl = false;
+  uint32_t wsl_maxw = 0, wsl_block = 1024;
+  size_t wsl_off_at = 0, wsl_band_at = 0;  // word offsets into d_wsl
+  uint32_t wsl_real = 0, wsl_padded = 0;   // live in-links, slot words
   std::vector<int32_t> row_of;  // scratch for orh_spf_run (all -1 between calls)
   // orh_spf_run's staged request on this graph (sources, ignore sets,
   // neighbour rows, batch order), keyed by the request: a repeated sweep
@@ -193,6 +203,10 @@ void free_graph_device(orh_graph* g) {
   (void)hipFree(g->d_wms);
   g->d_wms = nullptr;
   g->wms_dirty = true;
+  (void)hipFree(g->d_wsl);
+  g->d_wsl = nullptr;
+  g->d_wsl_cap = 0;
+  g->wsl_dirty = true;
   g->d_recs = nullptr;
   g->d_link = nullptr;
   g->d_rank_out = nullptr;
@@ -436,6 +450,103 @@ int sync_wms_layout(orh_graph* g) {
   return ORH_OK;
 }
 
+// kWmsSliced in-link slots: the sync_wms_layout words for a graph of any
+// degree, as a sliced ELL over the Cuthill-McKee ids. Slice s is the nodes
+// [64 s, 64 s + 64); its width is its largest live in-degree rounded up to 4
+// columns (the kernel reads 4 at a time); column k is the 64 words at
+// off[s] + 64 k, padding u = N. The waves of a batch own contiguous bands of
+// slices: band starts for 4, 8 and 16 waves, cut where the running column
+// count (+ 1 per slice, its own label) passes w / waves of the total.
+// wsl_block: the widest workgroup that still cuts the heaviest band by a
+// tenth against half as many waves (one indivisible wide slice bounds it)
+int sync_wms_sliced_layout(orh_graph* g) {
+  if (!g->wsl_dirty) return ORH_OK;
+  int rc = sync_ms_layout(g);
+  if (rc) return rc;
+  const uint32_t N = g->n_nodes;
+  g->wsl_ok = N > 0 && N <= 20480;
+  g->wsl_maxw = 0;
+  g->wsl_ovl = false;
+  g->wsl_real = g->wsl_padded = 0;
+  const uint32_t n_slice = (N + 63) / 64;
+  std::vector<uint32_t> off(n_slice + 1, 0), deg(N, 0);
+  for (uint32_t dv = 0; dv < N && g->wsl_ok; ++dv) {
+    const uint32_t v = g->ms_host_of[dv];
+    for (uint32_t e = g->row_ptr[v]; e < g->row_ptr[v + 1]; ++e) {
+      if (g->meta[e] & ORH_META_DOWN) continue;
+      const uint32_t w = g->w_in[e];
+      if (w == 0 || w > 0x7FFFu) {
+        g->wsl_ok = false;
+        break;
+      }
+      g->wsl_maxw = std::max(g->wsl_maxw, w);
+      ++deg[dv];
+    }
+  }
+  if (g->wsl_ok) {
+    for (uint32_t s = 0; s < n_slice; ++s) {
+      uint32_t width = 0;
+      for (uint32_t dv = s * 64; dv < std::min(N, s * 64 + 64); ++dv) width = std::max(width, deg[dv]);
+      off[s + 1] = off[s] + ((width + 3u) & ~3u) * 64u;
+    }
+    const size_t n_slots = off[n_slice];
+    const size_t off_at = n_slots, band_at = off_at + n_slice + 1, total = band_at + 5 + 9 + 17;
+    std::vector<uint32_t> st(total, N);
+    for (uint32_t dv = 0; dv < N; ++dv) {
+      const uint32_t v = g->ms_host_of[dv];
+      uint32_t k = 0;
+      for (uint32_t e = g->row_ptr[v]; e < g->row_ptr[v + 1]; ++e) {
+        if (g->meta[e] & ORH_META_DOWN) continue;
+        const uint32_t u = g->col[e];
+        if (g->overloaded[u]) g->wsl_ovl = true;
+        st[off[dv / 64] + 64u * k++ + (dv & 63u)] =
+            g->ms_dev_of[u] | (g->w_in[e] << 16) | (g->overloaded[u] ? 0x80000000u : 0u);
+        ++g->wsl_real;
+      }
+    }
+    g->wsl_padded = static_cast<uint32_t>(n_slots);
+    std::copy(off.begin(), off.end(), st.begin() + off_at);
+    uint64_t all = 0;
+    for (uint32_t s = 0; s < n_slice; ++s) all += (off[s + 1] - off[s]) / 64 + 1;
+    uint64_t heaviest[3] = {0, 0, 0};
+    uint32_t* band = st.data() + band_at;
+    for (uint32_t i = 0, waves = 4; i < 3; ++i, band += waves + 1, waves *= 2) {
+      uint64_t run = 0;
+      uint32_t s = 0;
+      for (uint32_t w = 0; w <= waves; ++w) {
+        // band w starts at the first slice whose running count reaches w / waves of the total
+        while (s < n_slice && w < waves && run * waves < all * w) run += (off[s + 1] - off[s]) / 64 + 1, ++s;
+        band[w] = w == waves ? n_slice : s;
+      }
+      for (uint32_t w = 0; w < waves; ++w) {
+        uint64_t c = 0;
+        for (uint32_t q = band[w]; q < band[w + 1]; ++q) c += (off[q + 1] - off[q]) / 64 + 1;
+        heaviest[i] = std::max(heaviest[i], c);
+      }
+    }
+    g->wsl_block = 256;
+    if (heaviest[1] * 10 <= heaviest[0] * 9) {
+      g->wsl_block = 512;
+      if (heaviest[2] * 10 <= heaviest[1] * 9) g->wsl_block = 1024;
+    }
+    orh_ctx* ctx = g->ctx;
+    if (st.size() > g->d_wsl_cap) {
+      (void)hipFree(g->d_wsl);
+      g->d_wsl = nullptr;
+      g->d_wsl_cap = 0;
+      ORH_HIP(ctx, hipMalloc(&g->d_wsl, st.size() * sizeof(uint32_t)));
+      g->d_wsl_cap = st.size();
+    }
+    ORH_HIP(ctx, hipMemcpyAsync(g->d_wsl, st.data(), st.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                ctx->stream));
+    ORH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // st is a local
+    g->wsl_off_at = off_at;
+    g->wsl_band_at = band_at;
+  }
+  g->wsl_dirty = false;
+  return ORH_OK;
+}
+
 uint64_t next_graph_gen() {
   static std::atomic<uint64_t> gen{0};
   return ++gen;
@@ -470,6 +581,7 @@ int upload_records(orh_graph* g, const std::vector<std::pair<uint32_t, uint32_t>
   ORH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging is a local
   g->ms_dirty = true;
   g->wms_dirty = true;
+  g->wsl_dirty = true;
   return ORH_OK;
 }
 
@@ -1041,6 +1153,7 @@ int orh_graph_apply_delta(orh_graph* g, uint32_t n_rows, const uint32_t* rows, c
   }
   g->ms_dirty = true;
   g->wms_dirty = true;
+  g->wsl_dirty = true;
   g->gen = next_graph_gen();  // staged requests hold neighbour lists of the old rows
   return ORH_OK;
 }
@@ -2114,14 +2227,14 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
   // fewest requested sources that take it (default 256: below, the fused
   // per-source search, which needs no neighbour rows, is the better plan)
   bool wms = false;
+  static const uint32_t wms_min = [] {
+    const char* e = getenv("ORH_WMS_MIN");
+    return e ? static_cast<uint32_t>(atoi(e)) : 256u;
+  }();
   {
     static const bool on = [] {
       const char* e = getenv("ORH_WMS");
       return !(e && e[0] == '0');
-    }();
-    static const uint32_t wms_min = [] {
-      const char* e = getenv("ORH_WMS_MIN");
-      return e ? static_cast<uint32_t>(atoi(e)) : 256u;
     }();
     if (on && ctx->spf_mode == orh::SpfMode::kAuto && !uniform && !has_ign && n_src >= wms_min &&
         (plan.variant == orh::SpfVariant::kDist16 || plan.variant == orh::SpfVariant::kDist32) &&
@@ -2131,6 +2244,30 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
       if (g->wms_ok) {
         wms = true;
         run_plan.variant = orh::SpfVariant::kWms;
+        rc = ensure_labels(ctx, (static_cast<size_t>(n_rows) + 2) / 2 + 1);  // the overflow row list
+        if (rc) return rc;
+      }
+    }
+  }
+  // the same sweep on a graph WMS declined, with sources of more than 32
+  // distinct neighbours (where the fused LDS search below does not apply and
+  // the sweep would run the two-phase per-source plan): the sliced multi-
+  // source kernel (spf_wms_sliced_kernel), flagged rows redone by that
+  // two-phase plan's own search. ORH_WMS_SLICED=0: off, today's plan (A/B);
+  // ORH_WMS_SLICED_ALL=1: also with <= 32 neighbours (A/B against kLdsNh)
+  bool wsl = false;
+  {
+    const char* on_e = getenv("ORH_WMS_SLICED");  // both read per run (tests flip them)
+    const char* all_e = getenv("ORH_WMS_SLICED_ALL");
+    const bool on = !(on_e && on_e[0] == '0'), all = all_e && all_e[0] == '1';
+    if (on && !wms && ctx->spf_mode == orh::SpfMode::kAuto && !uniform && !has_ign && n_src >= wms_min &&
+        (plan.variant == orh::SpfVariant::kDist16 || plan.variant == orh::SpfVariant::kDist32) &&
+        orh::wms_lds_bytes(N) <= ctx->lds_limit && plan.lds_bytes <= ctx->lds_limit && (max_nbr > 32 || all)) {
+      int rc = sync_wms_sliced_layout(g);
+      if (rc) return rc;
+      if (g->wsl_ok) {
+        wsl = true;
+        run_plan.variant = orh::SpfVariant::kWmsSliced;
         rc = ensure_labels(ctx, (static_cast<size_t>(n_rows) + 2) / 2 + 1);  // the overflow row list
         if (rc) return rc;
       }
@@ -2150,7 +2287,7 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
       const char* e = getenv("ORH_LDS_NH_MIN");
       return e ? static_cast<uint32_t>(atoi(e)) : 32u;
     }();
-    if (on && !wms && (has_ign || n_src >= lds_nh_min) && ctx->spf_mode == orh::SpfMode::kAuto && !uniform &&
+    if (on && !wms && !wsl && (has_ign || n_src >= lds_nh_min) && ctx->spf_mode == orh::SpfMode::kAuto && !uniform &&
         max_nbr <= 32 &&
         (plan.variant == orh::SpfVariant::kDist16 || plan.variant == orh::SpfVariant::kDist32) &&
         orh::lds_nh_bytes(N, false) <= ctx->lds_limit) {
@@ -2306,8 +2443,22 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
     hipError_t pre = hipGetLastError();
     if (pre != hipSuccess) { std::string m = "pending HIP error before spf launch (variant " + std::to_string(int(run_plan.variant)) + " rows " + std::to_string(n_rows) + ")"; return hip_fail(ctx, pre, m.c_str()); }
   }
-  if (run_plan.variant == orh::SpfVariant::kLdsNh || run_plan.variant == orh::SpfVariant::kWms)
+  if (run_plan.variant == orh::SpfVariant::kLdsNh || run_plan.variant == orh::SpfVariant::kWms || wsl)
     a.ovf_rows = reinterpret_cast<uint32_t*>(ctx->d_labels);
+  uint32_t wsl_block = 0;
+  if (wsl) {
+    a.dev_of = g->d_ms_dev_of;
+    a.wms_limit = 0xFFFEu - g->wsl_maxw;
+    a.wsl_slots = g->d_wsl;
+    a.wsl_off = g->d_wsl + g->wsl_off_at;
+    a.wsl_ovl = g->wsl_ovl ? 1u : 0u;
+    // ORH_WMS_SLICED_BLOCK=256|512|1024 (A/B): threads per batch instead of
+    // the layout's choice
+    const char* be = getenv("ORH_WMS_SLICED_BLOCK");  // read per run
+    const int bv = be ? atoi(be) : 0;
+    wsl_block = (bv == 256 || bv == 512 || bv == 1024) ? static_cast<uint32_t>(bv) : g->wsl_block;
+    a.wsl_band = g->d_wsl + g->wsl_band_at + (wsl_block == 256 ? 0u : wsl_block == 512 ? 5u : 14u);
+  }
   if (run_plan.variant == orh::SpfVariant::kWms) {
     a.dev_of = g->d_ms_dev_of;
     a.wms_slots = g->d_wms;
@@ -2328,6 +2479,7 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
   hipError_t e = run_plan.variant == orh::SpfVariant::kLdsNh
       ? orh::launch_spf_lds_nh(a, n_rows, g->ell_k, lds_nh_packed, run_plan.block, ctx->stream)
       : run_plan.variant == orh::SpfVariant::kWms ? orh::launch_spf_wms(a, n_rows, g->wms_k, ctx->lds_limit, ctx->stream)
+      : wsl ? orh::launch_spf_wms_sliced(plan, a, n_rows, wsl_block, ctx->lds_limit, ctx->stream)
       : orh::launch_spf(run_plan, a, n_rows, ctx->stream);
   if (e != hipSuccess) { std::string m = "spf kernel launch variant " + std::to_string(int(run_plan.variant)) + " rows " + std::to_string(n_rows) + " lds " + std::to_string(run_plan.lds_bytes) + " block " + std::to_string(run_plan.block) + " j " + std::to_string(run_plan.ms_j); return hip_fail(ctx, e, m.c_str()); }
 #ifdef ORH_DIAG_STAMPS
@@ -2381,7 +2533,13 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
   info.ms_threads = run_plan.variant == orh::SpfVariant::kMsBfs ? run_plan.block : 0;
   info.ms_skip = run_plan.variant == orh::SpfVariant::kMsBfs && a.ms_bw ? 1u : 0u;
   info.ms_direct = run_plan.variant == orh::SpfVariant::kMsBfs ? a.ms_direct
-                 : run_plan.variant == orh::SpfVariant::kWms && g->ms_identity ? 1u : 0u;
+                 : (run_plan.variant == orh::SpfVariant::kWms || wsl) && g->ms_identity ? 1u : 0u;
+  if (wsl) {
+    info.batch_sources = orh::wms_sources(N, ctx->lds_limit);
+    info.ms_threads = wsl_block;
+    info.wsl_links = g->wsl_real;
+    info.wsl_slots = g->wsl_padded;
+  }
   if (run_plan.variant == orh::SpfVariant::kMsBfs) {
 #ifdef ORH_EXP_MSBFS_ONLY  // timing experiment only (tools/diag_build.sh): no phase 2
     ctx->last_info = info;

@@ -5,6 +5,8 @@
   C3  3-tier Clos of ~2.5k nodes (full spine mesh) + 100k /64s over the
       RSWs (~54 each) and a seeded 5% anycast subset (2-8 advertisers),
       default and best-route selection                       c3_fabric()
+  C3w the same Clos with seeded metrics 1..64: weighted all-sources sweep
+      of a high-degree graph (tools/c3w_sweep.py)            c3_weighted_fabric()
   C4  50k-node WAN, log-normal metrics: single-link what-if SPFs and KSP2
       (src, dst) pairs                                       c4_wan()
   C5  4 areas x ~2.5k nodes, myNode in all four, 1M prefixes with random
@@ -76,6 +78,40 @@ def c2_weighted_grid(n: int = 100, max_metric: int = C2W_MAX_METRIC, seed: int =
                 metric[key] = rng.randint(1, max_metric)
             adj.metric = metric[key]
     return adj_dbs, prefixes
+
+
+C3W_SEED, C3W_MAX_METRIC = 3303, 64
+
+
+def weight_links(adj_dbs, lo: int, hi: int, seed: int, symmetric: bool = True):
+    """Give every adjacency a seeded metric uniform in [lo, hi], drawn in
+    adjacency order: one draw per link (its first appearance), the same in
+    both directions, when ``symmetric``; else one draw per direction."""
+    rng = random.Random(seed)
+    metric = {}
+    for db in adj_dbs:
+        a = db.thisNodeName
+        for adj in db.adjacencies:
+            if not symmetric:
+                adj.metric = rng.randint(lo, hi)
+                continue
+            b = adj.otherNodeName
+            key = (min(a, b), max(a, b))
+            if key not in metric:
+                metric[key] = rng.randint(lo, hi)
+            adj.metric = metric[key]
+    return adj_dbs
+
+
+def c3_weighted_fabric(num_nodes: int = 2500, max_metric: int = C3W_MAX_METRIC, seed: int = C3W_SEED,
+                       symmetric: bool = True, area: str = K_TESTING_AREA):
+    """C3's Clos with integer metrics (the weighted all-sources sweep of a
+    high-degree graph: spines of degree 39, FSWs of 84, RSWs of 8 at 2,500):
+    fabric(num_nodes, bug_compatible=False) with every link given a seeded
+    metric uniform in [1, max_metric] (weight_links). Returns (adj_dbs,
+    prefixes) like fabric."""
+    adj_dbs, prefixes = fabric(num_nodes, bug_compatible=False, area=area)
+    return weight_links(adj_dbs, 1, max_metric, seed, symmetric), prefixes
 
 
 def c4_wan(num_nodes: int = 50_000, seed: int = C4_SEED):
