@@ -189,6 +189,8 @@ typedef struct orh_spf_info {
                              written by the search kernel, no finalize pass) */
   uint32_t wsl_links;     /* sliced WMS: live in-links of the layout, else 0 */
   uint32_t wsl_slots;     /* sliced WMS: slot words of the layout, padding included, else 0 */
+  uint32_t hop_dist;      /* MS-BFS: the first-hop phase wrote the distance rows (the finalize
+                             pass the level rows alone; ORH_HOP_DIST=0 turns it off), else 0 */
 } orh_spf_info;
 int orh_last_spf_info(const orh_ctx* ctx, orh_spf_info* out);
 /* device time (HIP events on the context stream) of the last orh_spf_run;

@@ -446,6 +446,7 @@ class SpfSweep {
     d["batch_sources"] = i.batch_sources;
     d["hop_nodes"] = i.hop_nodes;
     d["hop_split"] = i.hop_split;
+    d["hop_dist"] = i.hop_dist;
     d["ms_threads"] = i.ms_threads;
     d["ms_skip"] = i.ms_skip;
     d["ms_direct"] = i.ms_direct;

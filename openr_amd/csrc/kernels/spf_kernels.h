@@ -126,6 +126,10 @@ struct HopArgs {
   // logical blocks (sources x tile phases); a grid smaller than this runs
   // persistent workgroups, each striding through its XCD's logical range
   uint32_t n_logical;
+  // level-row kernel: 1 = it also writes each source's u32 distance row from
+  // the level bytes it holds (the level-only ms_finalize_kernel ran before
+  // it); entries marked kLvlDirect stay as the search kernel wrote them
+  uint32_t write_dist;
 };
 
 enum class SpfVariant {
@@ -249,8 +253,11 @@ hipError_t launch_first_hop(HopArgs a, uint32_t max_nbr, hipStream_t s,
                             uint32_t* nodes_per_thread = nullptr, uint32_t* split = nullptr);
 // multi-source BFS plans, phase 2a: node-major level bytes -> requested dist
 // rows (host order) and u8 level rows of every row (a.lvl_rows), which the
-// first-hop phase reads instead of u32 distance rows
-hipError_t launch_ms_finalize(const SpfPlan& plan, SpfArgs a, uint32_t n_rows, hipStream_t s);
+// first-hop phase reads instead of u32 distance rows. write_dist = false: the
+// level rows alone (the first-hop phase writes the distance rows,
+// HopArgs::write_dist)
+hipError_t launch_ms_finalize(const SpfPlan& plan, SpfArgs a, uint32_t n_rows, hipStream_t s,
+                              bool write_dist = true);
 
 // recs[pos[i]] = vals[i] for i < n (device pointers)
 // recs[pos[i]] = vals[i], link[pos[i]] = links[i], rank[pos[i]] = ranks[i]

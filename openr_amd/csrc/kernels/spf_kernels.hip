@@ -322,8 +322,9 @@ __global__ __launch_bounds__(kMaxBlock) void spf_bfs_kernel(SpfArgs a) {
 // Levels leave the CU as they are found, as bytes in a node-major scratch
 // lvl[(batch * N + v) * S + b] (one S-byte block per node, written only by
 // the node's owner thread, so a store instruction's 64 lanes land in one
-// 2 KB span), and ms_finalize_kernel turns the scratch into host-order u32
-// rows with coalesced stores. (Measured alternatives: a row-major scratch
+// 2 KB span), and ms_finalize_kernel turns the scratch into host-order rows
+// with coalesced stores (u8 level rows; the u32 distance rows too, unless
+// the first-hop pass writes those, HopArgs::write_dist). (Measured alternatives: a row-major scratch
 // written per source bit issues ~5x more store instructions on the grid, where
 // a node's bits arrive a few at a time but different lanes get different bits;
 // dword stores for whole nibbles cost more than the stores they save.) Levels
@@ -800,8 +801,10 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
 
 // node-major level bytes -> host-order u32 distance rows, one workgroup per
 // (batch, 256-node host tile); per source bit b the 256 stores of a row are
-// contiguous
-template <class M>
+// contiguous. kDist = false: the u8 level rows alone (an 8-bit transpose);
+// the first-hop pass, which loads each source's level bytes anyway, writes
+// the u32 rows from them (HopArgs::write_dist)
+template <class M, bool kDist>
 __global__ __launch_bounds__(256) void ms_finalize_kernel(SpfArgs a, uint32_t tiles) {
   constexpr uint32_t kS = MsMask<M>::kS;
   __shared__ uint32_t* s_out[kS];
@@ -813,7 +816,7 @@ __global__ __launch_bounds__(256) void ms_finalize_kernel(SpfArgs a, uint32_t ti
   const uint32_t S = min(a.ms_width, a.n_rows - b0);
   if (threadIdx.x < S) {
     s_row[threadIdx.x] = a.order[b0 + threadIdx.x];
-    s_out[threadIdx.x] = dist_row(a.out_dist, a.scratch, a.n_out, N, s_row[threadIdx.x]);
+    if (kDist) s_out[threadIdx.x] = dist_row(a.out_dist, a.scratch, a.n_out, N, s_row[threadIdx.x]);
   }
   __syncthreads();
   if (i >= N) {  // level-row padding [N, pitch): "unreached" for the 16-byte reads
@@ -841,7 +844,7 @@ __global__ __launch_bounds__(256) void ms_finalize_kernel(SpfArgs a, uint32_t ti
     const uint32_t r = s_row[b];
     a.lvl_rows[static_cast<size_t>(r) * a.lvl_pitch + i] = static_cast<uint8_t>(l);
     // neighbour-only rows are read through their level row
-    if (l == kLvlDirect || r >= a.n_out) continue;
+    if (!kDist || l == kLvlDirect || r >= a.n_out) continue;
     __builtin_nontemporal_store(l == kLvlNone ? kInf : l * w0, &s_out[b][i]);
   }
 }
@@ -3145,6 +3148,33 @@ __global__ __launch_bounds__(kBlock) ORH_HOP_ATTR void first_hop_lvl_kernel(HopA
     bool own_direct = false;
 #pragma unroll
     for (uint32_t q = 0; q < kWords; ++q) own_direct |= has_byte_fe(ow[q]);
+    if (a.write_dist) {
+      // the source's own distance row from the level bytes just loaded (the
+      // level-only ms_finalize_kernel left it unwritten): once per tile, the
+      // source's own entry included (level 0). kLvlDirect entries are skipped:
+      // the search kernel wrote them, and dist_at / hop_entries read exactly
+      // those entries of this row back - no other, so a thread never reads an
+      // entry this kernel writes
+      uint32_t* od = dist_row(const_cast<uint32_t*>(a.dist), const_cast<uint32_t*>(a.scratch), a.n_out,
+                              N, i) + v0;
+      auto dist_of = [&](uint32_t k) -> uint32_t {
+        const uint32_t l = (ow[k / 4] >> ((k & 3u) * 8u)) & 0xFFu;
+        return l == kLvlNone ? kInf : l * w0;
+      };
+      if (!own_direct && v0 + kLvlPer <= N && (reinterpret_cast<uintptr_t>(od) & 15u) == 0u) {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (uint32_t q = 0; q < kWords; ++q) {
+          const u32x4 x = {dist_of(4 * q), dist_of(4 * q + 1), dist_of(4 * q + 2), dist_of(4 * q + 3)};
+          __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(od) + q);
+        }
+      } else {
+#pragma unroll
+        for (uint32_t k = 0; k < kLvlPer; ++k)
+          if (v0 + k < N && ((ow[k / 4] >> ((k & 3u) * 8u)) & 0xFFu) != kLvlDirect)
+            __builtin_nontemporal_store(dist_of(k), od + k);
+      }
+    }
     // d_s(v0 + k) where needed (the direct path; kInf: the source, which has
     // no next hops, and the padding past N) - not held for all k (VGPRs)
     auto own_dist = [&](uint32_t k) -> uint32_t {
@@ -3781,18 +3811,28 @@ hipError_t launch_first_hop(HopArgs a, uint32_t max_nbr, hipStream_t s, uint32_t
   return launch(first_hop_kernel, a, static_cast<uint32_t>(grid), kBlock, lds, s);
 }
 
-hipError_t launch_ms_finalize(const SpfPlan& plan, SpfArgs a, uint32_t n_rows, hipStream_t s) {
+template <bool kDist>
+static void launch_ms_finalize_as(const SpfPlan& plan, const SpfArgs& a, uint32_t grid, uint32_t tiles,
+                                  hipStream_t s) {
+  if (plan.mask_bytes == 2)
+    hipLaunchKernelGGL((ms_finalize_kernel<uint16_t, kDist>), dim3(grid), dim3(256), 0, s, a, tiles);
+  else if (plan.mask_bytes == 4)
+    hipLaunchKernelGGL((ms_finalize_kernel<uint32_t, kDist>), dim3(grid), dim3(256), 0, s, a, tiles);
+  else
+    hipLaunchKernelGGL((ms_finalize_kernel<uint64_t, kDist>), dim3(grid), dim3(256), 0, s, a, tiles);
+}
+
+hipError_t launch_ms_finalize(const SpfPlan& plan, SpfArgs a, uint32_t n_rows, hipStream_t s,
+                              bool write_dist) {
   if (plan.variant != SpfVariant::kMsBfs || n_rows == 0) return hipErrorInvalidValue;
   a.n_rows = n_rows;
   if (a.ms_width == 0 || a.ms_width > plan.mask_bytes * 8) return hipErrorInvalidValue;
   const uint32_t batches = (n_rows + a.ms_width - 1) / a.ms_width;
   const uint32_t tiles = (a.n_nodes + 255) / 256;
-  if (plan.mask_bytes == 2)
-    hipLaunchKernelGGL(ms_finalize_kernel<uint16_t>, dim3(batches * tiles), dim3(256), 0, s, a, tiles);
-  else if (plan.mask_bytes == 4)
-    hipLaunchKernelGGL(ms_finalize_kernel<uint32_t>, dim3(batches * tiles), dim3(256), 0, s, a, tiles);
+  if (write_dist)
+    launch_ms_finalize_as<true>(plan, a, batches * tiles, tiles, s);
   else
-    hipLaunchKernelGGL(ms_finalize_kernel<uint64_t>, dim3(batches * tiles), dim3(256), 0, s, a, tiles);
+    launch_ms_finalize_as<false>(plan, a, batches * tiles, tiles, s);
   return hipGetLastError();
 }
 

@@ -2568,8 +2568,20 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
       ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_ms2, 0));
       s2 = ctx->stream2;
     }
+    // The u32 distance rows of a finalize sweep (u16 / u32 masks): written by
+    // the first-hop pass from the level bytes each of its threads loads
+    // anyway, so ms_finalize_kernel writes the u8 level rows alone. That pass
+    // covers every output row 0..n_src-1 (one source each; neighbour-only rows
+    // r >= n_src have no distance row either way), and nothing reads d_dist
+    // between the two launches: on the deferred path both go to stream2 and
+    // ev_p2, which every reader of the rows joins, is recorded after the
+    // first-hop kernel. ORH_HOP_DIST=0: the rows from ms_finalize_kernel (A/B)
+    const char* hd = getenv("ORH_HOP_DIST");  // read per run (tests flip it)
+    const bool hop_dist = !(hd && hd[0] == '0') && !a.ms_direct && run_plan.mask_bytes <= 4;
+    h.write_dist = hop_dist ? 1u : 0u;
+    info.hop_dist = h.write_dist;
     if (!a.ms_direct) {
-      e = orh::launch_ms_finalize(run_plan, a, n_rows, s2);
+      e = orh::launch_ms_finalize(run_plan, a, n_rows, s2, !hop_dist);
       if (e != hipSuccess) return hip_fail(ctx, e, "multi-source finalize launch");
     }
     e = orh::launch_first_hop(h, max_nbr, s2, &info.hop_nodes, &info.hop_split);
