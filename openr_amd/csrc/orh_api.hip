@@ -39,7 +39,6 @@ struct orh_ctx {
   // reusable device staging for the exact kernel's request arrays
   uint32_t* d_req = nullptr;
   size_t d_req_cap = 0;
-  std::vector<uint32_t> req_key;
   // distance rows of neighbours that are not themselves requested sources
   uint32_t* d_scratch = nullptr;
   size_t d_scratch_cap = 0;  // in u32
@@ -87,6 +86,16 @@ struct orh_ctx {
   // sets), 2 every ignore-set batch the repair can take
   int repair_mode = 1;
   uint32_t rep_cap_a = 0, rep_cap_e = 0;  // LDS repair caps; 0 = by graph size (ORH_REPAIR_CAPS=A,E)
+};
+
+// orh_spf_run's request as staged in orh_graph::d_req (stage_request):
+// n_rows | srcs[n_rows] | ign_ptr[n_rows + 1] ign[..] | nbr_ptr[n_src + 1]
+// nbr_row[..] | order[n_rows], the offsets in words
+struct StagedRequest {
+  std::vector<uint32_t> key;  // graph generation + sources + ignore sets; empty: nothing staged
+  uint32_t n_rows = 0;        // sources + neighbour rows
+  uint32_t off_ign_ptr = 0, off_ign = 0, off_nbr_ptr = 0, off_nbr_row = 0, off_order = 0;
+  uint32_t xcd_group = 0;  // HopArgs::xcd_group
 };
 
 struct orh_graph {
@@ -153,8 +162,7 @@ struct orh_graph {
   // neither rebuilds nor uploads it, even when several graphs share a context
   uint32_t* d_req = nullptr;
   size_t d_req_cap = 0;
-  std::vector<uint32_t> req_key;
-  uint32_t req_xcd_group = 0;  // HopArgs::xcd_group of the staged request
+  StagedRequest staged;
   // what-if repair: per record, the record of the same link from the other
   // end; per link, its two CSR entries (~0 when absent); valid for rev_gen
   uint32_t* d_rev = nullptr;
@@ -193,7 +201,7 @@ void free_graph_device(orh_graph* g) {
   (void)hipFree(g->d_req);
   g->d_req = nullptr;
   g->d_req_cap = 0;
-  g->req_key.clear();
+  g->staged.key.clear();
   g->rev_gen = 0;
   g->d_name_rank = nullptr;
   g->d_ms_recs = nullptr;
@@ -632,7 +640,6 @@ int ensure_req(orh_ctx* ctx, size_t words) {
   if (words <= ctx->d_req_cap) return ORH_OK;
   hipFree(ctx->d_req);
   ctx->d_req = nullptr;
-  ctx->req_key.clear();
   const size_t cap = std::max<size_t>(words, 4096);
   ORH_HIP(ctx, hipMalloc(&ctx->d_req, cap * sizeof(uint32_t)));
   ctx->d_req_cap = cap;
@@ -644,7 +651,7 @@ int ensure_graph_req(orh_graph* g, size_t words) {
   hipFree(g->d_req);
   g->d_req = nullptr;
   g->d_req_cap = 0;
-  g->req_key.clear();
+  g->staged.key.clear();
   const size_t cap = std::max<size_t>(words, 4096);
   ORH_HIP(g->ctx, hipMalloc(&g->d_req, cap * sizeof(uint32_t)));
   g->d_req_cap = cap;
@@ -714,12 +721,6 @@ int ensure_bytes(orh_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes) {
 // summed in 64 bits by the reference, LinkState.h:22)
 bool wide_metrics(const orh_graph* g) {
   return g->sum_max_metric / 2 + g->max_metric >= 0xFFFFFFFFull;
-}
-
-// a staged request is reused when the stored key is this request's key
-// followed by `extra` words of staging offsets
-bool staged_key_matches(const std::vector<uint32_t>& stored, const std::vector<uint32_t>& key, size_t extra) {
-  return stored.size() == key.size() + extra && std::equal(key.begin(), key.end(), stored.begin());
 }
 
 int ensure_ms_lvl(orh_ctx* ctx, size_t bytes) {
@@ -932,7 +933,6 @@ int orh_graph_destroy(orh_graph* g) {
   drain_deferred(g->ctx);
   hipStreamSynchronize(g->ctx->stream);
   free_graph_device(g);
-  g->ctx->req_key.clear();  // the staged request may describe this graph
   delete g;
   return ORH_OK;
 }
@@ -1258,7 +1258,6 @@ static int run_exact(orh_graph* g, const orh_spf_request* req, uint32_t words, u
   }
   int rc = ensure_req(ctx, staging.size());
   if (rc) return rc;
-  ctx->req_key.clear();  // the staged request of orh_spf_run is overwritten
   ORH_HIP(ctx, hipMemcpyAsync(ctx->d_req, staging.data(), staging.size() * 4, hipMemcpyHostToDevice,
                               ctx->stream));
   ORH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging is a local
@@ -2019,13 +2018,643 @@ int orh_whatif_destroy(orh_whatif* job) {
 
 }  // extern "C"
 
+// ---- orh_spf_run's steps ----------------------------------------------------
+namespace {
+
+// what the steps know of a request
+struct SweepFacts {
+  uint32_t n_src, n_rows;  // requested sources; staged rows (sources + neighbour rows)
+  uint32_t max_nbr, words;  // most distinct neighbours of a source; first-hop words per node
+  bool uniform, has_ign;
+  uint32_t w0;  // the metric of every link when uniform
+  uint32_t flags;
+  int32_t use_link_metric;
+};
+
+// Stages the request in g->d_req, unless the request staged there already is
+// this one (g->staged.key). Phase 1 computes a distance row for every
+// requested source and for every distinct neighbour of one (the first-hop
+// phase reads them). Without ignore sets rows are shared by node: a neighbour
+// that is itself requested reuses its output row, the others get scratch
+// rows. With per-source ignore sets a source's neighbour rows are its own
+// (same ignore set).
+int stage_request(orh_graph* g, const orh_spf_request* req, bool has_ign) {
+  orh_ctx* ctx = g->ctx;
+  const uint32_t n_src = req->n_src;
+  const uint32_t n_ign = has_ign ? req->h_ignore_ptr[n_src] : 0u;
+  StagedRequest st;
+  // request key: graph generation + sources + ignore sets
+  std::vector<uint32_t>& key = st.key;
+  key.reserve(6 + n_src + (has_ign ? n_src + 1 + n_ign : 0));
+  const uint64_t gp = reinterpret_cast<uintptr_t>(g);
+  key.insert(key.end(), {static_cast<uint32_t>(gp), static_cast<uint32_t>(gp >> 32),
+                         static_cast<uint32_t>(g->gen), static_cast<uint32_t>(g->gen >> 32),
+                         n_src, has_ign ? 1u : 0u});
+  key.insert(key.end(), req->h_srcs, req->h_srcs + n_src);
+  if (has_ign) {
+    key.insert(key.end(), req->h_ignore_ptr, req->h_ignore_ptr + n_src + 1);
+    key.insert(key.end(), req->h_ignore_links, req->h_ignore_links + n_ign);
+  }
+  if (g->staged.key == key) return ORH_OK;
+  std::vector<uint32_t> srcs(req->h_srcs, req->h_srcs + n_src), nbr_ptr(n_src + 1, 0), nbr_row;
+  std::vector<uint32_t> ign_ptr, ign;
+  if (!has_ign) {
+    auto& ro = g->row_of;
+    for (uint32_t i = 0; i < n_src; ++i)
+      if (ro[req->h_srcs[i]] < 0) ro[req->h_srcs[i]] = static_cast<int32_t>(i);
+    for (uint32_t i = 0; i < n_src; ++i) {
+      const uint32_t s = req->h_srcs[i];
+      for (uint32_t k = g->dn_ptr[s]; k < g->dn_ptr[s + 1]; ++k) {
+        const uint32_t u = g->dn[k];
+        if (ro[u] < 0) {
+          ro[u] = static_cast<int32_t>(srcs.size());
+          srcs.push_back(u);
+        }
+        nbr_row.push_back(static_cast<uint32_t>(ro[u]));
+      }
+      nbr_ptr[i + 1] = static_cast<uint32_t>(nbr_row.size());
+    }
+    for (uint32_t u : srcs) ro[u] = -1;
+  } else {
+    ign_ptr.assign(1, 0);
+    auto add_set = [&](uint32_t i) {
+      std::vector<uint32_t> s(req->h_ignore_links + req->h_ignore_ptr[i],
+                              req->h_ignore_links + req->h_ignore_ptr[i + 1]);
+      std::sort(s.begin(), s.end());  // bsearch on device
+      ign.insert(ign.end(), s.begin(), s.end());
+      ign_ptr.push_back(static_cast<uint32_t>(ign.size()));
+    };
+    for (uint32_t i = 0; i < n_src; ++i) add_set(i);
+    for (uint32_t i = 0; i < n_src; ++i) {
+      const uint32_t s = req->h_srcs[i];
+      for (uint32_t k = g->dn_ptr[s]; k < g->dn_ptr[s + 1]; ++k) {
+        nbr_row.push_back(static_cast<uint32_t>(srcs.size()));
+        srcs.push_back(g->dn[k]);
+        add_set(i);
+      }
+      nbr_ptr[i + 1] = static_cast<uint32_t>(nbr_row.size());
+    }
+  }
+  st.n_rows = static_cast<uint32_t>(srcs.size());
+  {  // first-hop block order: one contiguous source range per XCD when the
+     // per-source work (neighbour rows) is even, else runs of 16 so heavy
+     // sources (Clos spines) still spread over the XCDs (A/B: C2 0.342 vs
+     // 0.350 ms, C3 0.231 vs 0.107 ms for contiguous vs runs of 16/64)
+    uint64_t sum = 0;
+    uint32_t mx = 0;
+    for (uint32_t i = 0; i < n_src; ++i) {
+      const uint32_t d = nbr_ptr[i + 1] - nbr_ptr[i];
+      sum += d;
+      mx = std::max(mx, d);
+    }
+    st.xcd_group = static_cast<uint64_t>(mx) * n_src <= 2 * sum ? 0u : 16u;
+  }
+  std::vector<uint32_t> staging;
+  staging.reserve(2 * srcs.size() + ign_ptr.size() + ign.size() + nbr_ptr.size() + nbr_row.size() + 1);
+  auto append = [&](const std::vector<uint32_t>& part) {
+    const uint32_t at = static_cast<uint32_t>(staging.size());
+    staging.insert(staging.end(), part.begin(), part.end());
+    return at;
+  };
+  staging.push_back(st.n_rows);
+  append(srcs);
+  st.off_ign_ptr = append(ign_ptr);
+  st.off_ign = append(ign);
+  st.off_nbr_ptr = append(nbr_ptr);
+  st.off_nbr_row = append(nbr_row);
+  // multi-source batches (consecutive runs of ms_width rows): rows in
+  // ascending Cuthill-McKee id of their source, so a batch's sources are
+  // neighbours. (Measured alternatives on C2: BFS balls of 32 rows - 10.6
+  // arrival levels per node and batch against 16.4 - swept in 0.92 ms
+  // against 0.77; dispatching the batches middle-out changed nothing.)
+  std::vector<uint32_t> order(st.n_rows);
+  for (uint32_t r = 0; r < st.n_rows; ++r) order[r] = r;
+  std::stable_sort(order.begin(), order.end(),
+                   [&](uint32_t x, uint32_t y) { return g->ms_dev_of[srcs[x]] < g->ms_dev_of[srcs[y]]; });
+  st.off_order = append(order);
+  drain_deferred(ctx);  // a deferred phase 2 may still read the staged request
+  int rc = ensure_graph_req(g, staging.size());
+  if (rc) return rc;
+  g->staged.key.clear();  // d_req no longer holds the request it names
+  ORH_HIP(ctx, hipMemcpyAsync(g->d_req, staging.data(), staging.size() * 4, hipMemcpyHostToDevice,
+                              ctx->stream));
+  ORH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging is a local
+  g->staged = std::move(st);
+  return ORH_OK;
+}
+
+bool env_is(const char* name, char c) {
+  const char* e = getenv(name);
+  return e && e[0] == c;
+}
+
+int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+
+// The environment knobs of orh_spf_run, all read by spf_knobs (the planners
+// and launchers of spf_kernels.hip read their own). The first group is read
+// once, at the first sweep of the process; the second at every sweep, because
+// tests flip those in-process. ORH_MS_DEFER_PRIO alone is read elsewhere: once
+// per context, when ensure_stream2 creates the second stream.
+struct SpfKnobs {
+  // ---- read once per process
+  // ORH_WMS=0: no kWms plan (A/B)
+  bool wms;
+  // ORH_WMS_MIN (256): the fewest requested sources that take kWms or
+  // kWmsSliced; below, the fused per-source search, which needs no neighbour
+  // rows, is the better plan
+  uint32_t wms_min;
+  // ORH_LDS_NH=0: no kLdsNh plan, the two-phase LDS plan instead (A/B)
+  bool lds_nh;
+  // ORH_LDS_NH_MIN (32): fewer sources without ignore sets keep the two-phase
+  // LDS plan: a lone search pays the fused kernel's per-bucket barriers with
+  // nothing beside it (C2's buildRouteDb after a metric change: spf(me)
+  // 1.15 ms fused against ~0.6 two-phase, profiles/r06/e_bench_phases.json)
+  uint32_t lds_nh_min;
+  // ORH_LDS_NH_BLOCK=64..1024 in steps of 64: threads per kLdsNh workgroup
+  // instead of the choice by source count (0)
+  uint32_t lds_nh_block;
+  // ORH_LDS_NH_DELTA_PCT (200): bucket width of the LDS searches (kLdsNh,
+  // kWms) in % of the mean live metric. Their relaxations cost LDS latency,
+  // not a global atomic, so wider buckets (fewer bucket barriers) pay: C2w
+  // sweep 45.5 / 30.8 / 28.9 / 29.0 / 31.4 ms at 25 / 100 / 200 / 400 / 800
+  // (profiles/r06/b_c2w_delta_block.txt)
+  uint32_t lds_nh_delta_pct;
+  // ORH_MS_DEFER=1: an ORH_SPF_DEFER_HOPS sweep's phase 2 goes to stream2, its
+  // level bytes in half p2_half of two. Off by default: the 32-sweep C2 step
+  // measured 23.1-23.2 ms deferred against 23.05 (2 lanes; 36.2 ms at 1
+  // lane), i.e. the GPU is already busy while a sweep's phase 2 runs - the
+  // searches and the phase-2 streams share the CUs, so starting the next
+  // search earlier only reorders the same work (profiles/r06/n_defer_ab.txt)
+  bool ms_defer;
+  // ---- read on every run
+  // ORH_BFS_NH_MAX (one per CU): the most sources that take kBfsNh; 0: off
+  uint32_t bfs_nh_max;
+  // ORH_WMS_SLICED=0: no kWmsSliced plan (A/B)
+  bool wms_sliced;
+  // ORH_WMS_SLICED_ALL=1: kWmsSliced also for sources of <= 32 neighbours
+  // (A/B against kLdsNh)
+  bool wms_sliced_all;
+  // ORH_WMS_SLICED_BLOCK=256|512|1024: threads per kWmsSliced batch instead of
+  // the layout's choice (0) (A/B)
+  uint32_t wms_sliced_block;
+  // ORH_MS_DIRECT=0: the rows of a host-order multi-source BFS through ms_lvl
+  // and ms_finalize instead of out of the search kernel (A/B)
+  bool ms_direct;
+  // ORH_WMS_SKIP=1: kWms's activity skip over the in-links' reach in layout
+  // ids. Its per-slice bitmap test costs more than the slices it skips once
+  // a round sweeps each band both ways: C2w distances 5.07 ms with it,
+  // 3.58 ms without (profiles/r06/v_wms_skip_ab.txt)
+  bool wms_skip;
+  // ORH_WMS_BAND=0: kWms over interleaved chunks, one sweep per round,
+  // instead of the band schedule (A/B)
+  bool wms_band;
+  // ORH_HOP_DIST=0: the distance rows of a finalize sweep from
+  // ms_finalize_kernel instead of the first-hop pass (A/B)
+  bool hop_dist;
+};
+
+SpfKnobs spf_knobs(const orh_ctx* ctx) {
+  static const SpfKnobs once = [] {
+    SpfKnobs k{};
+    k.wms = !env_is("ORH_WMS", '0');
+    k.wms_min = static_cast<uint32_t>(env_int("ORH_WMS_MIN", 256));
+    k.lds_nh = !env_is("ORH_LDS_NH", '0');
+    k.lds_nh_min = static_cast<uint32_t>(env_int("ORH_LDS_NH_MIN", 32));
+    const int b = env_int("ORH_LDS_NH_BLOCK", 0);
+    k.lds_nh_block = (b >= 64 && b <= 1024 && b % 64 == 0) ? static_cast<uint32_t>(b) : 0u;
+    const int pct = env_int("ORH_LDS_NH_DELTA_PCT", 200);
+    k.lds_nh_delta_pct = pct > 0 ? static_cast<uint32_t>(pct) : 200u;
+    k.ms_defer = env_is("ORH_MS_DEFER", '1');
+    return k;
+  }();
+  SpfKnobs k = once;
+  k.bfs_nh_max = static_cast<uint32_t>(env_int("ORH_BFS_NH_MAX", static_cast<int>(ctx->n_cu)));
+  k.wms_sliced = !env_is("ORH_WMS_SLICED", '0');
+  k.wms_sliced_all = env_is("ORH_WMS_SLICED_ALL", '1');
+  const int b = env_int("ORH_WMS_SLICED_BLOCK", 0);
+  k.wms_sliced_block = (b == 256 || b == 512 || b == 1024) ? static_cast<uint32_t>(b) : 0u;
+  k.ms_direct = !env_is("ORH_MS_DIRECT", '0');
+  k.wms_skip = env_is("ORH_WMS_SKIP", '1');
+  k.wms_band = !env_is("ORH_WMS_BAND", '0');
+  k.hop_dist = !env_is("ORH_HOP_DIST", '0');
+  return k;
+}
+
+// what phase 1 launches
+struct SweepPlan {
+  orh::SpfPlan run;    // the search
+  uint32_t n_rows;     // rows it searches: the staged ones, or one per source when the first hops are fused
+  bool wms, wsl;       // kWms; kWmsSliced (whose flagged rows the base plan's search redoes)
+  bool lds_nh_packed;  // kLdsNh with u32 labels first
+  bool fused;          // the search writes the first hops too: no phase 2
+  size_t label_words;  // d_labels entries to reserve (0: none)
+  uint32_t wsl_block;  // threads per kWmsSliced batch
+};
+
+// few rows: wide workgroups (a big frontier phase is split over more threads;
+// the rows do not fill the CUs anyway); many: narrow ones, several per CU
+uint32_t block_by_sources(const orh_ctx* ctx, uint32_t n_src) {
+  return n_src <= ctx->n_cu ? 1024u : n_src <= 2 * ctx->n_cu ? 512u : 256u;
+}
+
+// The plan of a sweep from the base plan (plan_spf) of its graph. The rules
+// in their order of precedence (a base plan is a BFS, a two-phase LDS or an
+// HBM plan, so rules of different bases never meet):
+//   kBfsNh      BFS base, at most bfs_nh_max sources
+//   kWms        many sources on a graph whose in-links fit 8 slots per node
+//   kWmsSliced  the same sweep where kWms declined
+//   kLdsNh      general metrics otherwise, sources of at most 32 neighbours
+//   kGlobalNh   HBM base
+int choose_plan(orh_graph* g, const orh::SpfPlan& base, const SweepFacts& f, const SpfKnobs& k,
+                SweepPlan* out) {
+  using V = orh::SpfVariant;
+  const orh_ctx* ctx = g->ctx;
+  const uint32_t N = g->n_nodes;
+  const bool automatic = ctx->spf_mode == orh::SpfMode::kAuto;
+  SweepPlan p{};
+  p.run = base;
+  p.n_rows = f.n_rows;
+  orh::ms_set_width(p.run, N, f.n_rows, ctx->n_cu, ctx->lds_limit,
+                    base.variant == V::kMsBfs && !device_busy_elsewhere(ctx));
+  // uniform metric, few sources: one fused BFS + first-hop workgroup per
+  // source instead of searching every neighbour row too
+  const bool bfs_base = base.variant == V::kMsBfs || base.variant == V::kBfs8 ||
+                        base.variant == V::kBfs16 || base.variant == V::kBfs32;
+  uint32_t blk = 0, jj = 0;
+  size_t lds = 0;
+  if (bfs_base && automatic && f.n_src <= k.bfs_nh_max &&
+      orh::bfs_nh_shape(N, f.words, ctx->lds_limit, &blk, &jj, &lds)) {
+    p.run.variant = V::kBfsNh;
+    p.run.block = blk;
+    p.run.lds_bytes = lds;
+    p.n_rows = f.n_src;
+  }
+  // the three plans for general metrics whose labels fit LDS start from the
+  // two-phase LDS plan; orh_set_spf_mode(1) (per-source) keeps that one
+  const bool weighted = automatic && !f.uniform && (base.variant == V::kDist16 || base.variant == V::kDist32);
+  const bool lds_nh_fits = orh::lds_nh_bytes(N, false) <= ctx->lds_limit;
+  // many sources: multi-source Bellman-Ford batches in LDS, then the first
+  // hops over the u32 rows (phase 2)
+  const bool many = weighted && !f.has_ign && f.n_src >= k.wms_min && orh::wms_lds_bytes(N) <= ctx->lds_limit;
+  if (many && k.wms && lds_nh_fits) {  // spf_wms_kernel; flagged rows redone by the u64 LDS search
+    int rc = sync_wms_layout(g);
+    if (rc) return rc;
+    p.wms = g->wms_ok;
+  }
+  // a graph kWms declined, with sources of more than 32 distinct neighbours
+  // (where kLdsNh does not apply and the sweep would run the two-phase plan):
+  // spf_wms_sliced_kernel, flagged rows redone by that plan's own search
+  if (many && !p.wms && k.wms_sliced && base.lds_bytes <= ctx->lds_limit &&
+      (f.max_nbr > 32 || k.wms_sliced_all)) {
+    int rc = sync_wms_sliced_layout(g);
+    if (rc) return rc;
+    p.wsl = g->wsl_ok;
+  }
+  if (p.wms || p.wsl) {
+    p.run.variant = p.wms ? V::kWms : V::kWmsSliced;
+    p.label_words = (static_cast<size_t>(p.n_rows) + 2) / 2 + 1;  // the overflow row list
+    if (p.wsl) p.wsl_block = k.wms_sliced_block ? k.wms_sliced_block : g->wsl_block;
+  } else if (weighted && k.lds_nh && (f.has_ign || f.n_src >= k.lds_nh_min) && f.max_nbr <= 32 && lds_nh_fits) {
+    // one search per source with the first hops fused (spf_lds_nh_kernel)
+    // instead of the two-phase LDS kernels, which also search every neighbour
+    // row and then stream 1 + deg rows per source
+    p.run.variant = V::kLdsNh;
+    p.lds_nh_packed = f.max_nbr <= 16;
+    p.n_rows = f.n_src;
+    p.run.block = k.lds_nh_block ? k.lds_nh_block : block_by_sources(ctx, f.n_src);
+    p.label_words = (static_cast<size_t>(f.n_src) + 2) / 2 + 1;  // the overflow row list
+  }
+  // HBM kernel: fuse the first hops into the search (one row per source)
+  // when the two-phase scheme would need extra neighbour rows (or the HBM
+  // kernel is forced)
+  if (base.variant == V::kGlobal && f.max_nbr <= 32 && ctx->spf_mode != orh::SpfMode::kGlobalTwoPhase &&
+      (ctx->spf_mode == orh::SpfMode::kGlobal || p.n_rows > f.n_src)) {
+    p.run.variant = V::kGlobalNh;
+    p.n_rows = f.n_src;
+    p.run.block = block_by_sources(ctx, f.n_src);
+    p.label_words = static_cast<size_t>(f.n_src) * N;
+  }
+  p.fused = p.run.variant == V::kGlobalNh || p.run.variant == V::kBfsNh || p.run.variant == V::kLdsNh;
+  *out = p;
+  return ORH_OK;
+}
+
+// SpfArgs of the search. A multi-source BFS gets its buffers here (layout,
+// level bytes and arrival log, level rows); *defer: its phase 2 goes to stream2
+int fill_spf_args(orh_graph* g, const SweepFacts& f, const SweepPlan& sp, const SpfKnobs& k, uint32_t* d_dist,
+                  uint32_t* d_nh, orh::SpfArgs* out, bool* defer) {
+  using V = orh::SpfVariant;
+  orh_ctx* ctx = g->ctx;
+  const uint32_t N = g->n_nodes;
+  const StagedRequest& st = g->staged;
+  orh::SpfArgs a{};
+  a.n_nodes = N;
+  a.n_out = f.n_src;
+  a.recs = g->d_recs;
+  a.link = g->d_link;
+  *defer = false;
+  if (sp.run.variant == V::kMsBfs) {
+    int rc = sync_ms_layout(g);
+    if (rc) return rc;
+    // the interval skip: opt-in for every sweep (ORH_MS_SKIP=1) or for the
+    // latency plan alone (ORH_MS_LATENCY=2)
+    a.ms_bw = g->ms_bw ? g->ms_bw : sp.run.ms_skip ? g->ms_bw_layout : 0u;
+    a.ms_width = sp.run.ms_width;
+    // host-order layout, u16 / u32 masks: the rows come out of the search
+    // kernel itself
+    a.ms_direct = k.ms_direct && g->ms_identity && sp.run.mask_bytes <= 4 ? 1u : 0u;
+    const size_t scratch =
+        a.ms_direct ? 0 : (orh::ms_scratch_bytes(sp.run, N, sp.n_rows) + 255) & ~size_t{255};
+    const size_t log_bytes = orh::ms_log_bytes(sp.run, sp.n_rows);
+    *defer = k.ms_defer && (f.flags & ORH_SPF_DEFER_HOPS) && !a.ms_direct && sp.n_rows == f.n_src;
+    const size_t halves = *defer ? 2 : 1;
+    rc = ensure_ms_lvl(ctx, halves * scratch + log_bytes);
+    if (rc) return rc;
+    a.ms_log = log_bytes ? reinterpret_cast<uint64_t*>(ctx->d_ms_lvl + halves * scratch) : nullptr;
+    a.recs = g->d_ms_recs;
+    a.dev_of = g->d_ms_dev_of;
+    a.host_of = g->d_ms_host_of;
+    a.ms_lvl = ctx->d_ms_lvl + (*defer ? ctx->p2_half * scratch : 0);
+    a.lvl_pitch = (N + 15u) & ~15u;
+    rc = ensure_lvl_rows(ctx, static_cast<size_t>(sp.n_rows) * a.lvl_pitch);
+    if (rc) return rc;
+    a.lvl_rows = ctx->d_lvl_rows;
+  }
+  a.order = g->d_req + st.off_order;
+  a.srcs = g->d_req + 1;
+  a.ignore_ptr = f.has_ign ? g->d_req + st.off_ign_ptr : nullptr;
+  a.ignore_links = f.has_ign ? g->d_req + st.off_ign : nullptr;
+  a.use_link_metric = f.use_link_metric;
+  a.w0 = f.w0;
+  // near/far width of the HBM kernel: the mean live metric (one BFS level
+  // when metrics are uniform); bucket width of the LDS searches
+  const uint32_t pct = sp.run.variant == V::kLdsNh || sp.wms ? k.lds_nh_delta_pct : ctx->delta_pct;
+  a.delta = f.uniform ? f.w0
+                      : std::max<uint32_t>(1u, static_cast<uint32_t>(static_cast<uint64_t>(g->mean_out) * pct / 100u));
+  a.out_dist = d_dist;
+  a.scratch = ctx->d_scratch;
+  a.labels = ctx->d_labels;
+  a.out_nh = d_nh;
+  a.words = f.words;
+  a.rank_out = g->d_rank_out;
+  if (sp.run.variant == V::kLdsNh || sp.wms || sp.wsl) a.ovf_rows = reinterpret_cast<uint32_t*>(ctx->d_labels);
+  if (sp.wsl) {
+    a.dev_of = g->d_ms_dev_of;
+    a.wms_limit = 0xFFFEu - g->wsl_maxw;
+    a.wsl_slots = g->d_wsl;
+    a.wsl_off = g->d_wsl + g->wsl_off_at;
+    a.wsl_ovl = g->wsl_ovl ? 1u : 0u;
+    a.wsl_band = g->d_wsl + g->wsl_band_at + (sp.wsl_block == 256 ? 0u : sp.wsl_block == 512 ? 5u : 14u);
+  }
+  if (sp.wms) {
+    a.dev_of = g->d_ms_dev_of;
+    a.wms_slots = g->d_wms;
+    a.wms_limit = 0xFFFEu - g->wms_maxw;
+    a.ms_bw = k.wms_skip ? g->ms_bw_layout : 0u;
+    a.recs_k = g->ell_k;
+    a.wms_band = k.wms_band ? 1u : 0u;
+  }
+  *out = a;
+  return ORH_OK;
+}
+
+// HopArgs of the first-hop phase over the rows of search `a`
+orh::HopArgs fill_hop_args(const orh_graph* g, const SweepFacts& f, const SweepPlan& sp, const orh::SpfArgs& a) {
+  const orh_ctx* ctx = g->ctx;
+  const StagedRequest& st = g->staged;
+  orh::HopArgs h{};
+  h.n_nodes = g->n_nodes;
+  h.n_out = f.n_src;
+  h.words = f.words;
+  h.ell_k = g->ell_k;
+  h.recs = g->d_recs;
+  h.link = g->d_link;
+  h.rank_out = g->d_rank_out;
+  h.overloaded = g->d_ovl;
+  h.srcs = a.srcs;
+  h.ignore_ptr = a.ignore_ptr;
+  h.ignore_links = a.ignore_links;
+  h.use_link_metric = f.use_link_metric;
+  h.nbr_ptr = g->d_req + st.off_nbr_ptr;
+  h.xcd_group = st.xcd_group;
+  h.nbr_row = g->d_req + st.off_nbr_row;
+  h.dist = a.out_dist;
+  h.scratch = ctx->d_scratch;
+  h.out_nh = a.out_nh;
+  h.lvl_rows = sp.run.variant == orh::SpfVariant::kMsBfs ? a.lvl_rows : nullptr;
+  h.lvl_pitch = a.lvl_pitch;
+  h.w0 = f.w0;
+  return h;
+}
+
+// Orders the context stream behind the deferred second phases this sweep's
+// buffers are shared with, then starts the sweep's clock
+int begin_sweep(orh_ctx* ctx, bool defer) {
+  if (!defer) {
+    join_deferred(ctx);  // earlier deferred sweeps share the scratch
+  } else if (ctx->p2_pending[ctx->p2_half]) {
+    // the search rewrites the half the phase 2 two sweeps back reads
+    ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[ctx->p2_half], 0));
+    ctx->p2_pending[ctx->p2_half] = false;
+  }
+  ORH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  return ORH_OK;
+}
+
+std::string plan_text(const SweepPlan& sp, bool shape) {
+  std::string m = "variant " + std::to_string(int(sp.run.variant)) + " rows " + std::to_string(sp.n_rows);
+  if (shape)
+    m += " lds " + std::to_string(sp.run.lds_bytes) + " block " + std::to_string(sp.run.block) + " j " +
+         std::to_string(sp.run.ms_j);
+  return m;
+}
+
+// the search; kWmsSliced redoes its flagged rows with the base plan's search
+int launch_phase1(orh_graph* g, const orh::SpfPlan& base, const SweepPlan& sp, const orh::SpfArgs& a) {
+  using V = orh::SpfVariant;
+  orh_ctx* ctx = g->ctx;
+  const hipError_t pre = hipGetLastError();
+  if (pre != hipSuccess)
+    return hip_fail(ctx, pre, ("pending HIP error before spf launch (" + plan_text(sp, false) + ")").c_str());
+  const hipError_t e =
+      sp.run.variant == V::kLdsNh
+          ? orh::launch_spf_lds_nh(a, sp.n_rows, g->ell_k, sp.lds_nh_packed, sp.run.block, ctx->stream)
+      : sp.wms ? orh::launch_spf_wms(a, sp.n_rows, g->wms_k, ctx->lds_limit, ctx->stream)
+      : sp.wsl ? orh::launch_spf_wms_sliced(base, a, sp.n_rows, sp.wsl_block, ctx->lds_limit, ctx->stream)
+               : orh::launch_spf(sp.run, a, sp.n_rows, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, ("spf kernel launch " + plan_text(sp, true)).c_str());
+  return ORH_OK;
+}
+
+#ifdef ORH_DIAG_STAMPS
+constexpr size_t kDiagWords = 16 + 4 * 4096;
+uint64_t* d_diag = nullptr;
+
+void diag_begin(orh_ctx* ctx, orh::SpfArgs* a) {
+  if (!d_diag) hipMalloc(&d_diag, kDiagWords * 8);
+  hipMemsetAsync(d_diag, 0, kDiagWords * 8, ctx->stream);
+  a->diag = d_diag;
+}
+
+void diag_report(orh_ctx* ctx) {
+  std::vector<uint64_t> h(kDiagWords);
+  hipMemcpyAsync(h.data(), d_diag, kDiagWords * 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipStreamSynchronize(ctx->stream);
+  if (h[4])
+    fprintf(stderr, "diag: waves %llu avg cycles %.0f barrier %.0f groups/wave %.1f levels %.1f max cycles %llu max levels %llu read %.0f proc %.0f\n",
+            (unsigned long long)h[4], double(h[0]) / h[4], double(h[1]) / h[4],
+            double(h[2]) / h[4], double(h[3]) / h[4], (unsigned long long)h[5], (unsigned long long)h[6], double(h[7]) / h[4], double(h[8]) / h[4]);
+  // per workgroup: duration, and how many workgroups shared its CU at any time
+  struct Wg { uint64_t t0, t1, cu; uint32_t lv, b; };
+  std::vector<Wg> wg;
+  for (uint32_t b = 0; b < 4096; ++b) {
+    const uint64_t* w = &h[16 + 4 * b];
+    if (!w[1]) continue;
+    const uint64_t hw = w[2];
+    // HW_ID: CU_ID [11:8], SH_ID [12], SE_ID [15:13]; XCC_ID in the high word
+    const uint64_t cu = ((hw >> 8) & 0xF) | (((hw >> 12) & 1) << 4) | (((hw >> 13) & 7) << 5) | ((hw >> 32) & 0xF) << 8;
+    wg.push_back({w[0], w[1], cu, static_cast<uint32_t>(w[3]), b});
+  }
+  if (wg.empty()) return;
+  uint64_t t_min = ~0ull, t_max = 0;
+  for (auto& x : wg) { t_min = std::min(t_min, x.t0); t_max = std::max(t_max, x.t1); }
+  std::vector<uint64_t> dur_solo, dur_shared;
+  uint64_t worst = 0; uint32_t worst_b = 0, worst_lv = 0; int worst_share = 0;
+  for (auto& x : wg) {
+    int share = 0;
+    for (auto& y : wg) if (&y != &x && y.cu == x.cu && y.t0 < x.t1 && x.t0 < y.t1) ++share;
+    (share ? dur_shared : dur_solo).push_back(x.t1 - x.t0);
+    if (x.t1 - x.t0 > worst) { worst = x.t1 - x.t0; worst_b = x.b; worst_lv = x.lv; worst_share = share; }
+  }
+  auto med = [](std::vector<uint64_t> v) { if (v.empty()) return 0.0; std::sort(v.begin(), v.end()); return double(v[v.size() / 2]); };
+  auto mx = [](const std::vector<uint64_t>& v) { uint64_t m = 0; for (auto x : v) m = std::max(m, x); return double(m); };
+  uint64_t last_start = 0;
+  for (auto& x : wg) last_start = std::max(last_start, x.t0 - t_min);
+  fprintf(stderr, "diag-wg: %zu wgs span %llu; solo %zu med %.0f max %.0f; shared %zu med %.0f max %.0f; worst wg %u (%u levels, %d partners) %llu; last start %llu\n",
+          wg.size(), (unsigned long long)(t_max - t_min), dur_solo.size(), med(dur_solo), mx(dur_solo),
+          dur_shared.size(), med(dur_shared), mx(dur_shared), worst_b, worst_lv, worst_share,
+          (unsigned long long)worst, (unsigned long long)last_start);
+}
+#endif
+
+// what orh_last_spf_info reports of the search (phase 2 adds its own shape)
+orh_spf_info search_info(const orh_graph* g, const SweepPlan& sp, const orh::SpfArgs& a) {
+  const bool ms = sp.run.variant == orh::SpfVariant::kMsBfs;
+  orh_spf_info info{};
+  info.variant = static_cast<int32_t>(sp.run.variant);
+  info.rows = sp.n_rows;
+  info.mask_bits = ms ? sp.run.mask_bytes * 8 : 0;
+  info.batch_sources = ms ? sp.run.ms_width : 0;
+  info.ms_threads = ms ? sp.run.block : 0;
+  info.ms_skip = ms && a.ms_bw ? 1u : 0u;
+  info.ms_direct = ms ? a.ms_direct : (sp.wms || sp.wsl) && g->ms_identity ? 1u : 0u;
+  if (sp.wsl) {
+    info.batch_sources = orh::wms_sources(g->n_nodes, g->ctx->lds_limit);
+    info.ms_threads = sp.wsl_block;
+    info.wsl_links = g->wsl_real;
+    info.wsl_slots = g->wsl_padded;
+  }
+  return info;
+}
+
+// the second stream of deferred second phases and its events, at first use
+int ensure_stream2(orh_ctx* ctx) {
+  if (ctx->stream2) return ORH_OK;
+  // ORH_MS_DEFER_PRIO (A/B): stream2's priority, -1 high / 1 low / 0 (default) normal
+  int lo = 0, hi = 0;
+  const int want = env_int("ORH_MS_DEFER_PRIO", 0);
+  if (want != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) {
+    ORH_HIP(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, want < 0 ? hi : lo));
+  } else {
+    ORH_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+  }
+  ORH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_ms2, hipEventDisableTiming));
+  ORH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p2[0], hipEventDisableTiming));
+  ORH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p2[1], hipEventDisableTiming));
+  return ORH_OK;
+}
+
+// Phase 2 of a sweep whose search leaves the first hops to it: the first-hop
+// pass, after ms_finalize_kernel when a multi-source BFS left level bytes.
+// *end: the stream the sweep ends on (stream2 when deferred)
+int launch_phase2(orh_graph* g, const SweepPlan& sp, const SpfKnobs& k, const orh::SpfArgs& a, orh::HopArgs h,
+                  uint32_t max_nbr, bool defer, orh_spf_info* info, hipStream_t* end) {
+  orh_ctx* ctx = g->ctx;
+  *end = ctx->stream;
+  ORH_HIP(ctx, hipEventRecord(ctx->evm, ctx->stream));
+  if (sp.fused) return ORH_OK;
+  if (sp.run.variant == orh::SpfVariant::kMsBfs) {
+#ifdef ORH_EXP_MSBFS_ONLY  // timing experiment only (tools/diag_build.sh): no phase 2
+    return ORH_OK;
+#endif
+    if (defer) {
+      // phase 2 on stream2 after this search; the context stream is free for
+      // the next sweep's search
+      int rc = ensure_stream2(ctx);
+      if (rc) return rc;
+      ORH_HIP(ctx, hipEventRecord(ctx->ev_ms2, ctx->stream));
+      ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_ms2, 0));
+      *end = ctx->stream2;
+    }
+    // The u32 distance rows of a finalize sweep (u16 / u32 masks): written by
+    // the first-hop pass from the level bytes each of its threads loads
+    // anyway, so ms_finalize_kernel writes the u8 level rows alone. That pass
+    // covers every output row 0..n_src-1 (one source each; neighbour-only rows
+    // r >= n_src have no distance row either way), and nothing reads d_dist
+    // between the two launches: on the deferred path both go to stream2 and
+    // ev_p2, which every reader of the rows joins, is recorded after the
+    // first-hop kernel
+    const bool hop_dist = k.hop_dist && !a.ms_direct && sp.run.mask_bytes <= 4;
+    h.write_dist = hop_dist ? 1u : 0u;
+    info->hop_dist = h.write_dist;
+    if (!a.ms_direct) {
+      const hipError_t e = orh::launch_ms_finalize(sp.run, a, sp.n_rows, *end, !hop_dist);
+      if (e != hipSuccess) return hip_fail(ctx, e, "multi-source finalize launch");
+    }
+  }
+  const hipError_t e = orh::launch_first_hop(h, max_nbr, *end, &info->hop_nodes, &info->hop_split);
+  if (e != hipSuccess) return hip_fail(ctx, e, "first-hop kernel launch");
+  if (defer) {
+    ORH_HIP(ctx, hipEventRecord(ctx->ev_p2[ctx->p2_half], *end));
+    ctx->p2_pending[ctx->p2_half] = true;
+    ctx->p2_half ^= 1u;
+  }
+  return ORH_OK;
+}
+
+// the sweep's end on stream `end`; last_kernel_ms is resolved lazily by
+// orh_spf_batch / orh_sync users
+int finish_sweep(orh_ctx* ctx, const orh_spf_info& info, uint32_t n_src, hipStream_t end) {
+  ctx->last_info = info;
+  ORH_HIP(ctx, hipEventRecord(ctx->ev1, end));
+  ctx->counters.spf_runs += n_src;
+  ctx->counters.spf_launches += 1;
+  ctx->counters.last_kernel_ms = -1.0;
+  return ORH_OK;
+}
+
+// orh_spf_batch's device rows, grown to n_u32 words
+bool ensure_batch(orh_ctx* ctx, size_t n_u32) {
+  if (n_u32 <= ctx->d_batch_cap) return true;
+  hipFree(ctx->d_batch);
+  ctx->d_batch = nullptr;
+  ctx->d_batch_cap = 0;
+  if (hipMalloc(&ctx->d_batch, n_u32 * 4) != hipSuccess) return false;
+  ctx->d_batch_cap = n_u32;
+  return true;
+}
+
+}  // namespace
+
 extern "C" {
 
-// Phase 1 computes a distance row for every requested source and for every
-// distinct neighbour of one (the first-hop phase reads them). Without ignore
-// sets rows are shared by node: a neighbour that is itself requested reuses
-// its output row, the others get scratch rows. With per-source ignore sets a
-// source's neighbour rows are its own (same ignore set).
+// One sweep: a dist row and the first-hop masks of every requested source.
+// Validate; the exact kernel or the what-if repair where they apply; else the
+// base plan of the graph, the staged request, the sweep's plan, the kernels'
+// arguments, the search (phase 1), the first hops (phase 2), the bookkeeping.
 int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32_t* d_dist,
                 uint32_t* d_nh) {
   if (!g || !req || (req->n_src && (!req->h_srcs || !d_dist || !d_nh)))
@@ -2048,21 +2677,27 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
                   "orh_spf_run: path metrics may reach 2^32 - 1 (use orh_spf_run_exact)");
     return run_exact(g, req, words, d_dist, nullptr, d_nh, nullptr);
   }
-  const bool uniform = !req->use_link_metric || g->min_out == g->max_out;
-  const uint32_t w0 = req->use_link_metric ? g->max_out : 1u;
+  SweepFacts f{};
+  f.n_src = n_src;
+  f.max_nbr = max_nbr;
+  f.words = words;
+  f.uniform = !req->use_link_metric || g->min_out == g->max_out;
+  f.has_ign = req->h_ignore_ptr != nullptr;
+  f.w0 = req->use_link_metric ? g->max_out : 1u;
+  f.flags = req->flags;
+  f.use_link_metric = req->use_link_metric;
   // any tentative value is at most (sum of link metrics) + max metric; BFS
   // levels at most (N - 1) * w0
-  const uint64_t bound = uniform ? static_cast<uint64_t>(N) * w0
+  const uint64_t bound = f.uniform ? static_cast<uint64_t>(N) * f.w0
       : req->use_link_metric ? g->sum_max_metric / 2 + g->max_metric
                              : static_cast<uint64_t>(g->n_links) + 1;
-  const bool has_ign = req->h_ignore_ptr != nullptr;
-  if (has_ign && ctx->spf_mode == orh::SpfMode::kAuto && max_nbr <= 32 && repair_eligible(g, req, words)) {
+  if (f.has_ign && ctx->spf_mode == orh::SpfMode::kAuto && max_nbr <= 32 && repair_eligible(g, req, words)) {
     hipSetDevice(ctx->device);
     return run_repair(g, req, d_dist, d_nh);
   }
-  const orh::SpfPlan plan =
-      orh::plan_spf(N, uniform, bound, g->ell_k, ctx->lds_limit, !has_ign, ctx->spf_mode);
-  if (plan.variant == orh::SpfVariant::kUnsupported)
+  const orh::SpfPlan base =
+      orh::plan_spf(N, f.uniform, bound, g->ell_k, ctx->lds_limit, !f.has_ign, ctx->spf_mode);
+  if (base.variant == orh::SpfVariant::kUnsupported)
     return fail(ctx, ORH_E_UNSUPPORTED, "orh_spf_run: no distance kernel for this graph (N=" +
                                             std::to_string(N) + ", path bound " +
                                             std::to_string(bound) + "; orh_spf_run_exact covers it)");
@@ -2070,543 +2705,39 @@ int orh_spf_run(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32
     return fail(ctx, ORH_E_UNSUPPORTED, "orh_spf_run: too many neighbours for the first-hop phase");
   hipSetDevice(ctx->device);
 
-  const uint32_t n_ign = has_ign ? req->h_ignore_ptr[n_src] : 0u;
-  // request key: graph generation + sources + ignore sets
-  std::vector<uint32_t> key;
-  key.reserve(6 + n_src + (has_ign ? n_src + 1 + n_ign : 0));
-  const uint64_t gp = reinterpret_cast<uintptr_t>(g);
-  key.insert(key.end(), {static_cast<uint32_t>(gp), static_cast<uint32_t>(gp >> 32),
-                         static_cast<uint32_t>(g->gen), static_cast<uint32_t>(g->gen >> 32),
-                         n_src, has_ign ? 1u : 0u});
-  key.insert(key.end(), req->h_srcs, req->h_srcs + n_src);
-  if (has_ign) {
-    key.insert(key.end(), req->h_ignore_ptr, req->h_ignore_ptr + n_src + 1);
-    key.insert(key.end(), req->h_ignore_links, req->h_ignore_links + n_ign);
-  }
-  // staged layout: srcs[n_rows] | ign_ptr[n_rows+1] ign[..] | nbr_ptr[n_src+1] nbr_row[..]
-  uint32_t n_rows = n_src;
-  size_t off_ign_ptr = 0, off_ign = 0, off_nbr_ptr = 0, off_nbr_row = 0, off_order = 0;
-  // the stored key carries six staging offsets after the request key
-  if (!staged_key_matches(g->req_key, key, 6)) {
-    std::vector<uint32_t> srcs(req->h_srcs, req->h_srcs + n_src), nbr_ptr(n_src + 1, 0), nbr_row;
-    std::vector<uint32_t> ign_ptr, ign;
-    std::vector<uint32_t> row_owner;  // source index whose ignore set a row uses
-    if (!has_ign) {
-      auto& ro = g->row_of;
-      for (uint32_t i = 0; i < n_src; ++i)
-        if (ro[req->h_srcs[i]] < 0) ro[req->h_srcs[i]] = static_cast<int32_t>(i);
-      for (uint32_t i = 0; i < n_src; ++i) {
-        const uint32_t s = req->h_srcs[i];
-        for (uint32_t k = g->dn_ptr[s]; k < g->dn_ptr[s + 1]; ++k) {
-          const uint32_t u = g->dn[k];
-          if (ro[u] < 0) {
-            ro[u] = static_cast<int32_t>(srcs.size());
-            srcs.push_back(u);
-          }
-          nbr_row.push_back(static_cast<uint32_t>(ro[u]));
-        }
-        nbr_ptr[i + 1] = static_cast<uint32_t>(nbr_row.size());
-      }
-      for (uint32_t u : srcs) ro[u] = -1;
-    } else {
-      ign_ptr.assign(1, 0);
-      auto add_set = [&](uint32_t i) {
-        std::vector<uint32_t> s(req->h_ignore_links + req->h_ignore_ptr[i],
-                                req->h_ignore_links + req->h_ignore_ptr[i + 1]);
-        std::sort(s.begin(), s.end());  // bsearch on device
-        ign.insert(ign.end(), s.begin(), s.end());
-        ign_ptr.push_back(static_cast<uint32_t>(ign.size()));
-      };
-      for (uint32_t i = 0; i < n_src; ++i) add_set(i);
-      for (uint32_t i = 0; i < n_src; ++i) {
-        const uint32_t s = req->h_srcs[i];
-        for (uint32_t k = g->dn_ptr[s]; k < g->dn_ptr[s + 1]; ++k) {
-          nbr_row.push_back(static_cast<uint32_t>(srcs.size()));
-          srcs.push_back(g->dn[k]);
-          add_set(i);
-        }
-        nbr_ptr[i + 1] = static_cast<uint32_t>(nbr_row.size());
-      }
-    }
-    n_rows = static_cast<uint32_t>(srcs.size());
-    {  // first-hop block order: one contiguous source range per XCD when the
-       // per-source work (neighbour rows) is even, else runs of 16 so heavy
-       // sources (Clos spines) still spread over the XCDs (A/B: C2 0.342 vs
-       // 0.350 ms, C3 0.231 vs 0.107 ms for contiguous vs runs of 16/64)
-      uint64_t sum = 0;
-      uint32_t mx = 0;
-      for (uint32_t i = 0; i < n_src; ++i) {
-        const uint32_t d = nbr_ptr[i + 1] - nbr_ptr[i];
-        sum += d;
-        mx = std::max(mx, d);
-      }
-      g->req_xcd_group = static_cast<uint64_t>(mx) * n_src <= 2 * sum ? 0u : 16u;
-    }
-    std::vector<uint32_t> staging;
-    staging.reserve(srcs.size() + ign_ptr.size() + ign.size() + nbr_ptr.size() + nbr_row.size() + 1);
-    staging.push_back(n_rows);
-    staging.insert(staging.end(), srcs.begin(), srcs.end());
-    off_ign_ptr = staging.size();
-    staging.insert(staging.end(), ign_ptr.begin(), ign_ptr.end());
-    off_ign = staging.size();
-    staging.insert(staging.end(), ign.begin(), ign.end());
-    off_nbr_ptr = staging.size();
-    staging.insert(staging.end(), nbr_ptr.begin(), nbr_ptr.end());
-    off_nbr_row = staging.size();
-    staging.insert(staging.end(), nbr_row.begin(), nbr_row.end());
-    // multi-source batches (consecutive runs of ms_width rows): rows in
-    // ascending Cuthill-McKee id of their source, so a batch's sources are
-    // neighbours. (Measured alternatives on C2: BFS balls of 32 rows - 10.6
-    // arrival levels per node and batch against 16.4 - swept in 0.92 ms
-    // against 0.77; dispatching the batches middle-out changed nothing.)
-    off_order = staging.size();
-    {
-      std::vector<uint32_t> order(n_rows);
-      for (uint32_t r = 0; r < n_rows; ++r) order[r] = r;
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        return g->ms_dev_of[srcs[x]] < g->ms_dev_of[srcs[y]];
-      });
-      staging.insert(staging.end(), order.begin(), order.end());
-    }
-    drain_deferred(ctx);  // a deferred phase 2 may still read the staged request
-    int rc = ensure_graph_req(g, staging.size());
-    if (rc) return rc;
-    ORH_HIP(ctx, hipMemcpyAsync(g->d_req, staging.data(), staging.size() * 4,
-                                hipMemcpyHostToDevice, ctx->stream));
-    ORH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging is a local
-    key.push_back(static_cast<uint32_t>(off_ign_ptr));
-    key.push_back(static_cast<uint32_t>(off_ign));
-    key.push_back(static_cast<uint32_t>(off_nbr_ptr));
-    key.push_back(static_cast<uint32_t>(off_nbr_row));
-    key.push_back(static_cast<uint32_t>(off_order));
-    key.push_back(n_rows);
-    g->req_key = std::move(key);
-  }
-  {
-    const auto& k = g->req_key;
-    const size_t t = k.size();
-    off_order = k[t - 2];
-    off_ign_ptr = k[t - 6];
-    off_ign = k[t - 5];
-    off_nbr_ptr = k[t - 4];
-    off_nbr_row = k[t - 3];
-    n_rows = k[t - 1];
-  }
-  // HBM kernel: fuse the first hops into the search (one row per source)
-  // when one mask word covers every source and the two-phase scheme would
-  // need extra neighbour rows (or the HBM kernel is forced)
-  orh::SpfPlan run_plan = plan;
-  orh::ms_set_width(run_plan, N, n_rows, ctx->n_cu, ctx->lds_limit,
-                    run_plan.variant == orh::SpfVariant::kMsBfs && !device_busy_elsewhere(ctx));
-  // uniform metric, at most ORH_BFS_NH_MAX sources (default: one per CU):
-  // one fused BFS + first-hop workgroup per source instead of searching
-  // every neighbour row too (ORH_BFS_NH_MAX=0 turns it off)
-  {
-    const bool bfs_plan = plan.variant == orh::SpfVariant::kMsBfs || plan.variant == orh::SpfVariant::kBfs8 ||
-                          plan.variant == orh::SpfVariant::kBfs16 || plan.variant == orh::SpfVariant::kBfs32;
-    uint32_t fused_max = ctx->n_cu;
-    if (const char* e = getenv("ORH_BFS_NH_MAX")) fused_max = static_cast<uint32_t>(atoi(e));
-    uint32_t blk = 0, jj = 0;
-    size_t lds = 0;
-    if (bfs_plan && ctx->spf_mode == orh::SpfMode::kAuto && n_src <= fused_max &&
-        orh::bfs_nh_shape(N, words, ctx->lds_limit, &blk, &jj, &lds)) {
-      run_plan.variant = orh::SpfVariant::kBfsNh;
-      run_plan.block = blk;
-      run_plan.lds_bytes = lds;
-      n_rows = n_src;
-    }
-  }
-  // general metrics whose labels fit LDS: one search per source with the
-  // first hops fused (spf_lds_nh_kernel) instead of the two-phase LDS kernels,
-  // which also search every neighbour row and then stream 1 + deg rows per
-  // source. ORH_LDS_NH=0: the two-phase plan (A/B); orh_set_spf_mode(1)
-  // (per-source) keeps it too
-  // many sources, general metrics, a graph whose in-links fit the ELL rows:
-  // 4-source Bellman-Ford batches in LDS (spf_wms_kernel), then the first
-  // hops over the u32 rows (phase 2). ORH_WMS=0 off (A/B); ORH_WMS_MIN: the
-  // fewest requested sources that take it (default 256: below, the fused
-  // per-source search, which needs no neighbour rows, is the better plan)
-  bool wms = false;
-  static const uint32_t wms_min = [] {
-    const char* e = getenv("ORH_WMS_MIN");
-    return e ? static_cast<uint32_t>(atoi(e)) : 256u;
-  }();
-  {
-    static const bool on = [] {
-      const char* e = getenv("ORH_WMS");
-      return !(e && e[0] == '0');
-    }();
-    if (on && ctx->spf_mode == orh::SpfMode::kAuto && !uniform && !has_ign && n_src >= wms_min &&
-        (plan.variant == orh::SpfVariant::kDist16 || plan.variant == orh::SpfVariant::kDist32) &&
-        orh::wms_lds_bytes(N) <= ctx->lds_limit && orh::lds_nh_bytes(N, false) <= ctx->lds_limit) {
-      int rc = sync_wms_layout(g);
-      if (rc) return rc;
-      if (g->wms_ok) {
-        wms = true;
-        run_plan.variant = orh::SpfVariant::kWms;
-        rc = ensure_labels(ctx, (static_cast<size_t>(n_rows) + 2) / 2 + 1);  // the overflow row list
-        if (rc) return rc;
-      }
-    }
-  }
-  // the same sweep on a graph WMS declined, with sources of more than 32
-  // distinct neighbours (where the fused LDS search below does not apply and
-  // the sweep would run the two-phase per-source plan): the sliced multi-
-  // source kernel (spf_wms_sliced_kernel), flagged rows redone by that
-  // two-phase plan's own search. ORH_WMS_SLICED=0: off, today's plan (A/B);
-  // ORH_WMS_SLICED_ALL=1: also with <= 32 neighbours (A/B against kLdsNh)
-  bool wsl = false;
-  {
-    const char* on_e = getenv("ORH_WMS_SLICED");  // both read per run (tests flip them)
-    const char* all_e = getenv("ORH_WMS_SLICED_ALL");
-    const bool on = !(on_e && on_e[0] == '0'), all = all_e && all_e[0] == '1';
-    if (on && !wms && ctx->spf_mode == orh::SpfMode::kAuto && !uniform && !has_ign && n_src >= wms_min &&
-        (plan.variant == orh::SpfVariant::kDist16 || plan.variant == orh::SpfVariant::kDist32) &&
-        orh::wms_lds_bytes(N) <= ctx->lds_limit && plan.lds_bytes <= ctx->lds_limit && (max_nbr > 32 || all)) {
-      int rc = sync_wms_sliced_layout(g);
-      if (rc) return rc;
-      if (g->wsl_ok) {
-        wsl = true;
-        run_plan.variant = orh::SpfVariant::kWmsSliced;
-        rc = ensure_labels(ctx, (static_cast<size_t>(n_rows) + 2) / 2 + 1);  // the overflow row list
-        if (rc) return rc;
-      }
-    }
-  }
-  // A few sources without ignore sets keep the two-phase LDS plan: a lone
-  // search pays the fused kernel's per-bucket barriers with nothing beside it
-  // (C2's buildRouteDb after a metric change: spf(me) 1.15 ms fused against
-  // ~0.6 two-phase, profiles/r06/e_bench_phases.json); ORH_LDS_NH_MIN (32)
-  bool lds_nh_packed = false;
-  {
-    static const bool on = [] {
-      const char* e = getenv("ORH_LDS_NH");
-      return !(e && e[0] == '0');
-    }();
-    static const uint32_t lds_nh_min = [] {
-      const char* e = getenv("ORH_LDS_NH_MIN");
-      return e ? static_cast<uint32_t>(atoi(e)) : 32u;
-    }();
-    if (on && !wms && !wsl && (has_ign || n_src >= lds_nh_min) && ctx->spf_mode == orh::SpfMode::kAuto && !uniform &&
-        max_nbr <= 32 &&
-        (plan.variant == orh::SpfVariant::kDist16 || plan.variant == orh::SpfVariant::kDist32) &&
-        orh::lds_nh_bytes(N, false) <= ctx->lds_limit) {
-      run_plan.variant = orh::SpfVariant::kLdsNh;
-      lds_nh_packed = max_nbr <= 16;
-      n_rows = n_src;
-      // few rows: wide workgroups (latency); many: narrow ones, several per CU
-      static const uint32_t blk_env = [] {
-        const char* e = getenv("ORH_LDS_NH_BLOCK");
-        const int b = e ? atoi(e) : 0;
-        return (b >= 64 && b <= 1024 && b % 64 == 0) ? static_cast<uint32_t>(b) : 0u;
-      }();
-      run_plan.block = blk_env ? blk_env
-                     : n_src <= ctx->n_cu ? 1024u : n_src <= 2 * ctx->n_cu ? 512u : 256u;
-      int rc = ensure_labels(ctx, (static_cast<size_t>(n_src) + 2) / 2 + 1);  // the overflow row list
-      if (rc) return rc;
-    }
-  }
-  if (plan.variant == orh::SpfVariant::kGlobal && max_nbr <= 32 &&
-      ctx->spf_mode != orh::SpfMode::kGlobalTwoPhase &&
-      (ctx->spf_mode == orh::SpfMode::kGlobal || n_rows > n_src)) {
-    run_plan.variant = orh::SpfVariant::kGlobalNh;
-    n_rows = n_src;
-    // few rows: wider workgroups (a big frontier phase is split over more
-    // threads; the rows do not fill the CUs anyway)
-    run_plan.block = n_src <= ctx->n_cu ? 1024u : n_src <= 2 * ctx->n_cu ? 512u : 256u;
-    int rc = ensure_labels(ctx, static_cast<size_t>(n_src) * N);
-    if (rc) return rc;
-  }
-  const bool fused = run_plan.variant == orh::SpfVariant::kGlobalNh ||
-                     run_plan.variant == orh::SpfVariant::kBfsNh ||
-                     run_plan.variant == orh::SpfVariant::kLdsNh;
-  const size_t n_extra = n_rows - n_src;
-  if (n_extra) {
-    int rc = ensure_scratch(ctx, n_extra * N);
-    if (rc) return rc;
-  }
+  int rc = stage_request(g, req, f.has_ign);
+  if (rc) return rc;
+  f.n_rows = g->staged.n_rows;
+  const SpfKnobs knobs = spf_knobs(ctx);
+  SweepPlan sp{};
+  rc = choose_plan(g, base, f, knobs, &sp);
+  if (rc) return rc;
+  if (sp.label_words) rc = ensure_labels(ctx, sp.label_words);
+  if (rc) return rc;
+  if (sp.n_rows > n_src) rc = ensure_scratch(ctx, static_cast<size_t>(sp.n_rows - n_src) * N);
+  if (rc) return rc;
 
   orh::SpfArgs a{};
-  a.n_nodes = N;
-  a.n_out = n_src;
-  a.recs = g->d_recs;
-  a.link = g->d_link;
   bool defer = false;  // this sweep's phase 2 goes to stream2
-  if (run_plan.variant == orh::SpfVariant::kMsBfs) {
-    int rc = sync_ms_layout(g);
-    if (rc) return rc;
-    // the interval skip: opt-in for every sweep (ORH_MS_SKIP=1) or for the
-    // latency plan alone (ORH_MS_LATENCY=2)
-    a.ms_bw = g->ms_bw ? g->ms_bw : run_plan.ms_skip ? g->ms_bw_layout : 0u;
-    a.ms_width = run_plan.ms_width;
-    // host-order layout, u16 / u32 masks: the rows come out of the search
-    // kernel itself (ORH_MS_DIRECT=0: through ms_lvl and ms_finalize, A/B)
-    const char* de = getenv("ORH_MS_DIRECT");  // read per run (tests flip it)
-    const bool direct_on = !(de && de[0] == '0');
-    a.ms_direct = direct_on && g->ms_identity && run_plan.mask_bytes <= 4 ? 1u : 0u;
-    const size_t scratch =
-        a.ms_direct ? 0 : (orh::ms_scratch_bytes(run_plan, N, n_rows) + 255) & ~size_t{255};
-    const size_t log_bytes = orh::ms_log_bytes(run_plan, n_rows);
-    // ORH_SPF_DEFER_HOPS: the level bytes in half p2_half of two. Off unless
-    // ORH_MS_DEFER=1: the 32-sweep C2 step measured 23.1-23.2 ms deferred
-    // against 23.05 (2 lanes; 36.2 ms at 1 lane), i.e. the GPU is already
-    // busy while a sweep's phase 2 runs - the searches and the phase-2
-    // streams share the CUs, so starting the next search earlier only
-    // reorders the same work (profiles/r06/n_defer_ab.txt)
-    static const bool defer_on = [] {
-      const char* e = getenv("ORH_MS_DEFER");
-      return e && e[0] == '1';
-    }();
-    defer = defer_on && (req->flags & ORH_SPF_DEFER_HOPS) && !a.ms_direct && n_extra == 0;
-    const size_t halves = defer ? 2 : 1;
-    rc = ensure_ms_lvl(ctx, halves * scratch + log_bytes);
-    if (rc) return rc;
-    a.ms_log = log_bytes ? reinterpret_cast<uint64_t*>(ctx->d_ms_lvl + halves * scratch) : nullptr;
-    a.recs = g->d_ms_recs;
-    a.dev_of = g->d_ms_dev_of;
-    a.host_of = g->d_ms_host_of;
-    a.ms_lvl = ctx->d_ms_lvl + (defer ? ctx->p2_half * scratch : 0);
-    a.lvl_pitch = (N + 15u) & ~15u;
-    rc = ensure_lvl_rows(ctx, static_cast<size_t>(n_rows) * a.lvl_pitch);
-    if (rc) return rc;
-    a.lvl_rows = ctx->d_lvl_rows;
-  }
-  a.order = g->d_req + off_order;
-  a.srcs = g->d_req + 1;
-  a.ignore_ptr = has_ign ? g->d_req + off_ign_ptr : nullptr;
-  a.ignore_links = has_ign ? g->d_req + off_ign : nullptr;
-  a.use_link_metric = req->use_link_metric;
-  a.w0 = w0;
-  // near/far width of the HBM kernel: the mean live metric (one BFS level
-  // when metrics are uniform)
-  a.delta = uniform ? w0
-                    : std::max<uint32_t>(1u, static_cast<uint32_t>(
-                                                 static_cast<uint64_t>(g->mean_out) * ctx->delta_pct / 100u));
-  if (run_plan.variant == orh::SpfVariant::kLdsNh || run_plan.variant == orh::SpfVariant::kWms) {
-    // ORH_LDS_NH_DELTA_PCT: bucket width of the LDS search in % of the mean
-    // live metric. Its relaxations cost LDS latency, not a global atomic, so
-    // wider buckets (fewer bucket barriers) pay: C2w sweep 45.5 / 30.8 / 28.9 /
-    // 29.0 / 31.4 ms at 25 / 100 / 200 / 400 / 800 (profiles/r06/b_c2w_delta_block.txt)
-    static const uint32_t pct = [] {
-      const char* e = getenv("ORH_LDS_NH_DELTA_PCT");
-      const int v = e ? atoi(e) : 200;
-      return v > 0 ? static_cast<uint32_t>(v) : 200u;
-    }();
-    a.delta = std::max<uint32_t>(1u, static_cast<uint32_t>(static_cast<uint64_t>(g->mean_out) * pct / 100u));
-  }
-  a.out_dist = d_dist;
-  a.scratch = ctx->d_scratch;
-  a.labels = ctx->d_labels;
-  a.out_nh = d_nh;
-  a.words = words;
-  a.rank_out = g->d_rank_out;
+  rc = fill_spf_args(g, f, sp, knobs, d_dist, d_nh, &a, &defer);
+  if (rc) return rc;
+  const orh::HopArgs h = fill_hop_args(g, f, sp, a);
 
-  orh::HopArgs h{};
-  h.n_nodes = N;
-  h.n_out = n_src;
-  h.words = words;
-  h.ell_k = g->ell_k;
-  h.recs = g->d_recs;
-  h.link = g->d_link;
-  h.rank_out = g->d_rank_out;
-  h.overloaded = g->d_ovl;
-  h.srcs = a.srcs;
-  h.ignore_ptr = a.ignore_ptr;
-  h.ignore_links = a.ignore_links;
-  h.use_link_metric = req->use_link_metric;
-  h.nbr_ptr = g->d_req + off_nbr_ptr;
-  h.xcd_group = g->req_xcd_group;
-  h.nbr_row = g->d_req + off_nbr_row;
-  h.dist = d_dist;
-  h.scratch = ctx->d_scratch;
-  h.out_nh = d_nh;
-  h.lvl_rows = run_plan.variant == orh::SpfVariant::kMsBfs ? a.lvl_rows : nullptr;
-  h.lvl_pitch = a.lvl_pitch;
-  h.w0 = w0;
-
-  if (!defer) {
-    join_deferred(ctx);  // earlier deferred sweeps share the scratch
-  } else if (ctx->p2_pending[ctx->p2_half]) {
-    // the search rewrites the half the phase 2 two sweeps back reads
-    ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[ctx->p2_half], 0));
-    ctx->p2_pending[ctx->p2_half] = false;
-  }
-  ORH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  rc = begin_sweep(ctx, defer);
+  if (rc) return rc;
 #ifdef ORH_DIAG_STAMPS
-  static uint64_t* d_diag = nullptr;
-  constexpr size_t kDiagWords = 16 + 4 * 4096;
-  if (!d_diag) hipMalloc(&d_diag, kDiagWords * 8);
-  hipMemsetAsync(d_diag, 0, kDiagWords * 8, ctx->stream);
-  a.diag = d_diag;
+  diag_begin(ctx, &a);
 #endif
-  {
-    hipError_t pre = hipGetLastError();
-    if (pre != hipSuccess) { std::string m = "pending HIP error before spf launch (variant " + std::to_string(int(run_plan.variant)) + " rows " + std::to_string(n_rows) + ")"; return hip_fail(ctx, pre, m.c_str()); }
-  }
-  if (run_plan.variant == orh::SpfVariant::kLdsNh || run_plan.variant == orh::SpfVariant::kWms || wsl)
-    a.ovf_rows = reinterpret_cast<uint32_t*>(ctx->d_labels);
-  uint32_t wsl_block = 0;
-  if (wsl) {
-    a.dev_of = g->d_ms_dev_of;
-    a.wms_limit = 0xFFFEu - g->wsl_maxw;
-    a.wsl_slots = g->d_wsl;
-    a.wsl_off = g->d_wsl + g->wsl_off_at;
-    a.wsl_ovl = g->wsl_ovl ? 1u : 0u;
-    // ORH_WMS_SLICED_BLOCK=256|512|1024 (A/B): threads per batch instead of
-    // the layout's choice
-    const char* be = getenv("ORH_WMS_SLICED_BLOCK");  // read per run
-    const int bv = be ? atoi(be) : 0;
-    wsl_block = (bv == 256 || bv == 512 || bv == 1024) ? static_cast<uint32_t>(bv) : g->wsl_block;
-    a.wsl_band = g->d_wsl + g->wsl_band_at + (wsl_block == 256 ? 0u : wsl_block == 512 ? 5u : 14u);
-  }
-  if (run_plan.variant == orh::SpfVariant::kWms) {
-    a.dev_of = g->d_ms_dev_of;
-    a.wms_slots = g->d_wms;
-    a.wms_limit = 0xFFFEu - g->wms_maxw;
-    // the in-links' reach in layout ids: the activity skip, opt-in
-    // (ORH_WMS_SKIP=1). Its per-slice bitmap test costs more than the slices
-    // it skips once a round sweeps each band both ways: C2w distances 5.07 ms
-    // with it, 3.58 ms without (profiles/r06/v_wms_skip_ab.txt)
-    const char* skip_e = getenv("ORH_WMS_SKIP");  // read per run (tests flip it)
-    const bool skip = skip_e && skip_e[0] == '1';
-    a.ms_bw = skip ? g->ms_bw_layout : 0u;
-    a.recs_k = g->ell_k;
-    // the band schedule (ORH_WMS_BAND=0: interleaved chunks, one sweep per
-    // round, A/B)
-    const char* band_e = getenv("ORH_WMS_BAND");  // read per run (tests flip it)
-    a.wms_band = (band_e && band_e[0] == '0') ? 0u : 1u;
-  }
-  hipError_t e = run_plan.variant == orh::SpfVariant::kLdsNh
-      ? orh::launch_spf_lds_nh(a, n_rows, g->ell_k, lds_nh_packed, run_plan.block, ctx->stream)
-      : run_plan.variant == orh::SpfVariant::kWms ? orh::launch_spf_wms(a, n_rows, g->wms_k, ctx->lds_limit, ctx->stream)
-      : wsl ? orh::launch_spf_wms_sliced(plan, a, n_rows, wsl_block, ctx->lds_limit, ctx->stream)
-      : orh::launch_spf(run_plan, a, n_rows, ctx->stream);
-  if (e != hipSuccess) { std::string m = "spf kernel launch variant " + std::to_string(int(run_plan.variant)) + " rows " + std::to_string(n_rows) + " lds " + std::to_string(run_plan.lds_bytes) + " block " + std::to_string(run_plan.block) + " j " + std::to_string(run_plan.ms_j); return hip_fail(ctx, e, m.c_str()); }
+  rc = launch_phase1(g, base, sp, a);
+  if (rc) return rc;
 #ifdef ORH_DIAG_STAMPS
-  {
-    std::vector<uint64_t> h(kDiagWords);
-    hipMemcpyAsync(h.data(), d_diag, kDiagWords * 8, hipMemcpyDeviceToHost, ctx->stream);
-    hipStreamSynchronize(ctx->stream);
-    if (h[4])
-      fprintf(stderr, "diag: waves %llu avg cycles %.0f barrier %.0f groups/wave %.1f levels %.1f max cycles %llu max levels %llu read %.0f proc %.0f\n",
-              (unsigned long long)h[4], double(h[0]) / h[4], double(h[1]) / h[4],
-              double(h[2]) / h[4], double(h[3]) / h[4], (unsigned long long)h[5], (unsigned long long)h[6], double(h[7]) / h[4], double(h[8]) / h[4]);
-    // per workgroup: duration, and how many workgroups shared its CU at any time
-    struct Wg { uint64_t t0, t1, cu; uint32_t lv, b; };
-    std::vector<Wg> wg;
-    for (uint32_t b = 0; b < 4096; ++b) {
-      const uint64_t* w = &h[16 + 4 * b];
-      if (!w[1]) continue;
-      const uint64_t hw = w[2];
-      // HW_ID: CU_ID [11:8], SH_ID [12], SE_ID [15:13]; XCC_ID in the high word
-      const uint64_t cu = ((hw >> 8) & 0xF) | (((hw >> 12) & 1) << 4) | (((hw >> 13) & 7) << 5) | ((hw >> 32) & 0xF) << 8;
-      wg.push_back({w[0], w[1], cu, static_cast<uint32_t>(w[3]), b});
-    }
-    if (!wg.empty()) {
-      uint64_t t_min = ~0ull, t_max = 0;
-      for (auto& x : wg) { t_min = std::min(t_min, x.t0); t_max = std::max(t_max, x.t1); }
-      std::vector<uint64_t> dur_solo, dur_shared;
-      uint64_t worst = 0; uint32_t worst_b = 0, worst_lv = 0; int worst_share = 0;
-      for (auto& x : wg) {
-        int share = 0;
-        for (auto& y : wg) if (&y != &x && y.cu == x.cu && y.t0 < x.t1 && x.t0 < y.t1) ++share;
-        (share ? dur_shared : dur_solo).push_back(x.t1 - x.t0);
-        if (x.t1 - x.t0 > worst) { worst = x.t1 - x.t0; worst_b = x.b; worst_lv = x.lv; worst_share = share; }
-      }
-      auto med = [](std::vector<uint64_t> v) { if (v.empty()) return 0.0; std::sort(v.begin(), v.end()); return double(v[v.size() / 2]); };
-      auto mx = [](const std::vector<uint64_t>& v) { uint64_t m = 0; for (auto x : v) m = std::max(m, x); return double(m); };
-      uint64_t last_start = 0;
-      for (auto& x : wg) last_start = std::max(last_start, x.t0 - t_min);
-      fprintf(stderr, "diag-wg: %zu wgs span %llu; solo %zu med %.0f max %.0f; shared %zu med %.0f max %.0f; worst wg %u (%u levels, %d partners) %llu; last start %llu\n",
-              wg.size(), (unsigned long long)(t_max - t_min), dur_solo.size(), med(dur_solo), mx(dur_solo),
-              dur_shared.size(), med(dur_shared), mx(dur_shared), worst_b, worst_lv, worst_share,
-              (unsigned long long)worst, (unsigned long long)last_start);
-    }
-  }
+  diag_report(ctx);
 #endif
-  ORH_HIP(ctx, hipEventRecord(ctx->evm, ctx->stream));
-  orh_spf_info info{};
-  info.variant = static_cast<int32_t>(run_plan.variant);
-  info.rows = n_rows;
-  info.mask_bits = run_plan.variant == orh::SpfVariant::kMsBfs ? run_plan.mask_bytes * 8 : 0;
-  info.batch_sources = run_plan.variant == orh::SpfVariant::kMsBfs ? run_plan.ms_width : 0;
-  info.ms_threads = run_plan.variant == orh::SpfVariant::kMsBfs ? run_plan.block : 0;
-  info.ms_skip = run_plan.variant == orh::SpfVariant::kMsBfs && a.ms_bw ? 1u : 0u;
-  info.ms_direct = run_plan.variant == orh::SpfVariant::kMsBfs ? a.ms_direct
-                 : (run_plan.variant == orh::SpfVariant::kWms || wsl) && g->ms_identity ? 1u : 0u;
-  if (wsl) {
-    info.batch_sources = orh::wms_sources(N, ctx->lds_limit);
-    info.ms_threads = wsl_block;
-    info.wsl_links = g->wsl_real;
-    info.wsl_slots = g->wsl_padded;
-  }
-  if (run_plan.variant == orh::SpfVariant::kMsBfs) {
-#ifdef ORH_EXP_MSBFS_ONLY  // timing experiment only (tools/diag_build.sh): no phase 2
-    ctx->last_info = info;
-    ORH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    return ORH_OK;
-#endif
-    hipStream_t s2 = ctx->stream;
-    if (defer) {
-      // phase 2 on stream2 after this search; the context stream is free for
-      // the next sweep's search
-      if (!ctx->stream2) {
-        // ORH_MS_DEFER_PRIO (A/B): stream2's priority, -1 high / 1 low / 0 (default) normal
-        int lo = 0, hi = 0;
-        const char* pe = getenv("ORH_MS_DEFER_PRIO");
-        const int want = pe ? atoi(pe) : 0;
-        if (want != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) {
-          ORH_HIP(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, want < 0 ? hi : lo));
-        } else {
-          ORH_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-        }
-        ORH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_ms2, hipEventDisableTiming));
-        ORH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p2[0], hipEventDisableTiming));
-        ORH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p2[1], hipEventDisableTiming));
-      }
-      ORH_HIP(ctx, hipEventRecord(ctx->ev_ms2, ctx->stream));
-      ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_ms2, 0));
-      s2 = ctx->stream2;
-    }
-    // The u32 distance rows of a finalize sweep (u16 / u32 masks): written by
-    // the first-hop pass from the level bytes each of its threads loads
-    // anyway, so ms_finalize_kernel writes the u8 level rows alone. That pass
-    // covers every output row 0..n_src-1 (one source each; neighbour-only rows
-    // r >= n_src have no distance row either way), and nothing reads d_dist
-    // between the two launches: on the deferred path both go to stream2 and
-    // ev_p2, which every reader of the rows joins, is recorded after the
-    // first-hop kernel. ORH_HOP_DIST=0: the rows from ms_finalize_kernel (A/B)
-    const char* hd = getenv("ORH_HOP_DIST");  // read per run (tests flip it)
-    const bool hop_dist = !(hd && hd[0] == '0') && !a.ms_direct && run_plan.mask_bytes <= 4;
-    h.write_dist = hop_dist ? 1u : 0u;
-    info.hop_dist = h.write_dist;
-    if (!a.ms_direct) {
-      e = orh::launch_ms_finalize(run_plan, a, n_rows, s2, !hop_dist);
-      if (e != hipSuccess) return hip_fail(ctx, e, "multi-source finalize launch");
-    }
-    e = orh::launch_first_hop(h, max_nbr, s2, &info.hop_nodes, &info.hop_split);
-    if (e != hipSuccess) return hip_fail(ctx, e, "first-hop kernel launch");
-    if (defer) {
-      ORH_HIP(ctx, hipEventRecord(ctx->ev_p2[ctx->p2_half], s2));
-      ctx->p2_pending[ctx->p2_half] = true;
-      ctx->p2_half ^= 1u;
-      ctx->last_info = info;
-      ORH_HIP(ctx, hipEventRecord(ctx->ev1, s2));
-      ctx->counters.spf_runs += n_src;
-      ctx->counters.spf_launches += 1;
-      ctx->counters.last_kernel_ms = -1.0;
-      return ORH_OK;
-    }
-  } else if (!fused) {
-    e = orh::launch_first_hop(h, max_nbr, ctx->stream, &info.hop_nodes, &info.hop_split);
-    if (e != hipSuccess) return hip_fail(ctx, e, "first-hop kernel launch");
-  }
-  ctx->last_info = info;
-  ORH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->counters.spf_runs += n_src;
-  ctx->counters.spf_launches += 1;
-  ctx->counters.last_kernel_ms = -1.0;  // resolved lazily by orh_spf_batch / orh_sync users
-  return ORH_OK;
+  orh_spf_info info = search_info(g, sp, a);
+  hipStream_t end = ctx->stream;
+  rc = launch_phase2(g, sp, knobs, a, h, max_nbr, defer, &info, &end);
+  if (rc) return rc;
+  return finish_sweep(ctx, info, n_src, end);
 }
 
 int orh_spf_batch(orh_graph* g, const orh_spf_request* req, uint32_t words, uint32_t* h_dist,
@@ -2617,14 +2748,8 @@ int orh_spf_batch(orh_graph* g, const orh_spf_request* req, uint32_t words, uint
   if (!h_dist || !h_nh) return fail(ctx, ORH_E_INVALID, "orh_spf_batch: null output");
   const size_t nd = static_cast<size_t>(req->n_src) * g->n_nodes;
   hipSetDevice(ctx->device);
-  if (nd * (1 + words) > ctx->d_batch_cap) {
-    hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr;
-    ctx->d_batch_cap = 0;
-    if (hipMalloc(&ctx->d_batch, nd * (1 + words) * 4) != hipSuccess)
-      return fail(ctx, ORH_E_NOMEM, "orh_spf_batch: device allocation failed");
-    ctx->d_batch_cap = nd * (1 + words);
-  }
+  if (!ensure_batch(ctx, nd * (1 + words)))
+    return fail(ctx, ORH_E_NOMEM, "orh_spf_batch: device allocation failed");
   uint32_t* d_dist = ctx->d_batch;
   uint32_t* d_nh = ctx->d_batch + nd;
   int rc = orh_spf_run(g, req, words, d_dist, d_nh);
@@ -2652,14 +2777,8 @@ int orh_spf_batch_pinned(orh_graph* g, const orh_spf_request* req, uint32_t word
   if (req->n_src == 0) return ORH_OK;
   const size_t nd = static_cast<size_t>(req->n_src) * g->n_nodes;
   hipSetDevice(ctx->device);
-  if (nd * (1 + words) > ctx->d_batch_cap) {
-    hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr;
-    ctx->d_batch_cap = 0;
-    if (hipMalloc(&ctx->d_batch, nd * (1 + words) * 4) != hipSuccess)
-      return fail(ctx, ORH_E_NOMEM, "orh_spf_batch_pinned: device allocation failed");
-    ctx->d_batch_cap = nd * (1 + words);
-  }
+  if (!ensure_batch(ctx, nd * (1 + words)))
+    return fail(ctx, ORH_E_NOMEM, "orh_spf_batch_pinned: device allocation failed");
   if (nd * (1 + words) > ctx->h_pinned_cap) {
     if (ctx->h_pinned) hipHostFree(ctx->h_pinned);
     ctx->h_pinned = nullptr;
