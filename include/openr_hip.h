@@ -179,7 +179,8 @@ typedef struct orh_spf_info {
   uint32_t rows;       /* distance rows searched (sources + neighbour rows) */
   uint32_t mask_bits;  /* MS-BFS: source-mask width (64, 32 or 16), else 0 */
   uint32_t hop_nodes;  /* first-hop phase: nodes per thread over u8 level rows
-                          (16 or 4), 1 for the u32-row kernel, 0 when fused */
+                          (8, 16 with ORH_HOP_NODES=16, or 4), 1 for the u32-row kernel,
+                          0 when fused */
   uint32_t hop_split;  /* first-hop phase: workgroups per source */
   uint32_t batch_sources; /* MS-BFS, sliced WMS: sources per workgroup (<= mask_bits), else 0 */
   uint32_t ms_threads;    /* MS-BFS: threads per workgroup (1024: the latency plan); sliced WMS:

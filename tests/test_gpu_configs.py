@@ -4,10 +4,10 @@ oracle (``-m gpu``).
 Each sweep test asserts which kernel plan ran (orh_last_spf_info), so the
 variant the bench times is the variant that is checked:
 
-  C2 100x100 grid, all 10,000 sources   MS-BFS u32 masks + first_hop_lvl<16>;
+  C2 100x100 grid, all 10,000 sources   MS-BFS u32 masks + first_hop_lvl<8>;
                                         opt-in u64 masks and interval skip
   ladder 2 x 4,100 (BFS depth > 254)    MS-BFS levels >= 254 written directly
-                                        (kLvlDirect) + first_hop_lvl<16>
+                                        (kLvlDirect) + first_hop_lvl<8>
   ladder 2 x 300, all sources           kLvlDirect + first_hop_lvl<4>
   150x150 grid (N = 22,500)             MS-BFS u16 masks (u32 exceeds LDS)
   C3 Clos (2,472 nodes)                 all 288 spines + sampled others
