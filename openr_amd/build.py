@@ -24,10 +24,11 @@ EXT = sysconfig.get_config_var("EXT_SUFFIX")
 HOST_MOD = os.path.join(PKG, "_openr_host" + EXT)
 ARCH = os.environ.get("OPENR_HIP_ARCH", "gfx950")
 
-HIP_SRCS = [os.path.join(CSRC, "orh_api.hip"), os.path.join(CSRC, "kernels", "spf_kernels.hip"),
-            os.path.join(CSRC, "kernels", "route_kernels.hip"),
-            os.path.join(CSRC, "kernels", "whatif_kernels.hip"),
-            os.path.join(CSRC, "kernels", "ksp_kernels.hip")]
+HIP_SRCS = [os.path.join(CSRC, "orh_api.hip")] + [
+    os.path.join(CSRC, "kernels", f + ".hip")
+    for f in ("spf_msbfs_kernels", "spf_lds_kernels", "spf_wms_kernels", "spf_bfs_kernels",
+              "spf_hop_kernels", "spf_hbm_kernels", "spf_dist_kernels", "spf_exact_kernels", "spf_plan",
+              "route_kernels", "whatif_kernels", "ksp_kernels")]
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("link_state.cpp", "prefix_state.cpp", "spf_solver.cpp",
                                                    "rib_policy.cpp", "thrift_compact.cpp",
                                                    "decision_ingest.cpp", "multi_device.cpp", "whatif_batch.cpp",
@@ -81,7 +82,7 @@ def build_hip_lib(force: bool = False) -> str:
               "-Wno-unused-value", "-Wno-unused-result", "-o", obj + ".tmp", src])
         os.replace(obj + ".tmp", obj)
 
-    with ThreadPoolExecutor(max(1, len(todo))) as ex:
+    with ThreadPoolExecutor(max(1, min(16, len(todo)))) as ex:
         list(ex.map(compile_one, todo))
     if force or todo or _stale(HIP_LIB, objs):
         tmp = HIP_LIB + ".tmp"

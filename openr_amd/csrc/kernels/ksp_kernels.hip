@@ -33,23 +33,10 @@
 #include <cstdlib>
 
 #include "ksp_kernels.h"
-#include "spf_kernels.h"  // edge record flags
+#include "spf_device.h"  // edge record flags, kInf, ignored()
 
 namespace orh {
 namespace {
-
-constexpr uint32_t kInf = 0xFFFFFFFFu;
-
-__device__ inline bool ign_has(const uint32_t* ign, uint32_t n, uint32_t link) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const uint32_t x = ign[mid];
-    if (x == link) return true;
-    if (x < link) lo = mid + 1; else hi = mid;
-  }
-  return false;
-}
 
 // inserts link; 0 = already present, 1 = inserted, 2 = table too full
 __device__ inline uint32_t visit(uint32_t* tab, uint32_t cap, uint32_t* count, uint32_t link) {
@@ -89,7 +76,7 @@ __device__ inline Cand next_cand(const KspArgs& a, const uint32_t* d, uint32_t s
     const uint32_t dp = d[p];
     if (dp == kInf) return;
     const uint32_t l = a.link[q];
-    if (n_ign && ign_has(ign, n_ign, l)) return;
+    if (n_ign && ignored(ign, n_ign, l)) return;
     const uint32_t q2 = a.rev[q];
     const uint2 back = a.recs[q2];  // p -> v: p's metric, p's overload bit
     if (p != s && (back.x & ORH_REC_ROW_OVL)) return;
@@ -295,7 +282,7 @@ __global__ __launch_bounds__(kWaveWaves * 64) void ksp_trace_wave_kernel(KspArgs
               p = rec.x & ORH_REC_COL_MASK;
               const uint32_t dp = d[p];
               l = a.link[q];
-              if (dp != kInf && !(n_ign && ign_has(ign, n_ign, l))) {
+              if (dp != kInf && !(n_ign && ignored(ign, n_ign, l))) {
                 const uint32_t qq = a.rev[q];
                 const uint2 back = a.recs[qq];  // p -> v: p's metric and overload bit
                 if ((p == s || !(back.x & ORH_REC_ROW_OVL)) && static_cast<uint64_t>(dp) + back.y == dv) {

@@ -31,15 +31,16 @@
 //                         a request whose A or edge list outgrows LDS is
 //                         flagged, repaired again with its state in a global
 //                         slot sized for the whole graph, and only when the
-//                         slots run out re-searched by spf_global_nh_kernel
-//                         with the flags as its row mask
+//                         slots run out re-searched by
+//                         spf_global_nh_async_kernel with the flags as its
+//                         row mask
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
-#include "spf_kernels.h"  // edge record flags
+#include "spf_device.h"  // edge record flags, ignored()
 #include "whatif_kernels.h"
 
 namespace orh {
@@ -48,17 +49,6 @@ namespace {
 constexpr uint32_t kSlotBlock = 1024;  // slot pass: few large affected sets, one per CU
 constexpr uint32_t kInfD = 0xFFFFFFFFu;
 constexpr unsigned long long kInfLab = 0xFFFFFFFF00000000ull;  // {dist = inf, mask = 0}
-
-__device__ inline bool is_ignored(const uint32_t* ign, uint32_t n, uint32_t link) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const uint32_t x = ign[mid];
-    if (x == link) return true;
-    if (x < link) lo = mid + 1; else hi = mid;
-  }
-  return false;
-}
 
 // lattice meet of a label and the candidate {d, nh}: a smaller distance
 // replaces, an equal one ORs the mask
@@ -214,7 +204,7 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
 
   // boundary labels from predecessors outside A; edges from those inside
   auto pred = [&](const uint2& rec, uint32_t q, auto&& inside, auto&& outside) {
-    if (n_ign && is_ignored(ign, n_ign, a.link[q])) return;
+    if (n_ign && ignored(ign, n_ign, a.link[q])) return;
     const uint32_t p = rec.x & ORH_REC_COL_MASK;
     const uint32_t q2 = a.rev[q];
     const uint2 back = a.recs[q2];  // p -> v: p's metric and p's overload bit

@@ -1716,7 +1716,7 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
   }
   if (n_slots == 0) {
     // no slot fits the budget: the requests that outgrew tier 2 are searched
-    // in full (spf_global_nh_kernel with the flags as its row mask)
+    // in full (spf_global_nh_async_kernel with the flags as its row mask)
     orh::SpfPlan fp = orh::plan_spf(N, job->uniform, job->bound, g->ell_k, ctx->lds_limit, false,
                                     orh::SpfMode::kGlobal);
     fp.variant = orh::SpfVariant::kGlobalNh;
@@ -2154,7 +2154,8 @@ int env_int(const char* name, int unset) {
 }
 
 // The environment knobs of orh_spf_run, all read by spf_knobs (the planners
-// and launchers of spf_kernels.hip read their own). The first group is read
+// and launchers of the kernel units read theirs through LaunchKnobs,
+// kernels/spf_launch.h). The first group is read
 // once, at the first sweep of the process; the second at every sweep, because
 // tests flip those in-process. ORH_MS_DEFER_PRIO alone is read elsewhere: once
 // per context, when ensure_stream2 creates the second stream.
