@@ -174,6 +174,10 @@ int orh_set_repair_mode(orh_ctx* ctx, int mode);
                                    batches in LDS, then the first-hop phase */
 #define ORH_VARIANT_WMS_SLICED 14 /* the same for graphs with nodes of any degree: the in-links
                                      in a sliced-ELL layout in global memory */
+#define ORH_VARIANT_WMS_WIDE 15 /* the sliced form with u32 labels and full u32 metrics: the sweeps
+                                   the two above decline for a live metric > 0x7FFF alone (4 sources
+                                   per batch, 2 where 16 B a node do not fit LDS; every row final).
+                                   ORH_WMS_WIDE=0 turns the plan off */
 typedef struct orh_spf_info {
   int32_t variant;     /* ORH_VARIANT_* of the distance phase */
   uint32_t rows;       /* distance rows searched (sources + neighbour rows) */
@@ -182,16 +186,22 @@ typedef struct orh_spf_info {
                           (8, 16 with ORH_HOP_NODES=16, or 4), 1 for the u32-row kernel,
                           0 when fused */
   uint32_t hop_split;  /* first-hop phase: workgroups per source */
-  uint32_t batch_sources; /* MS-BFS, sliced WMS: sources per workgroup (<= mask_bits), else 0 */
-  uint32_t ms_threads;    /* MS-BFS: threads per workgroup (1024: the latency plan); sliced WMS:
-                             threads per batch; else 0 */
+  uint32_t batch_sources; /* MS-BFS, sliced and wide WMS: sources per workgroup (<= mask_bits),
+                             else 0 */
+  uint32_t ms_threads;    /* MS-BFS: threads per workgroup (1024: the latency plan); sliced and
+                             wide WMS: threads per batch; else 0 */
   uint32_t ms_skip;       /* MS-BFS: interval skip on (latency plan or ORH_MS_SKIP=1) */
   uint32_t ms_direct;     /* MS-BFS / WMS: the node layout kept the host order (MS-BFS: rows
                              written by the search kernel, no finalize pass) */
-  uint32_t wsl_links;     /* sliced WMS: live in-links of the layout, else 0 */
-  uint32_t wsl_slots;     /* sliced WMS: slot words of the layout, padding included, else 0 */
+  uint32_t wsl_links;     /* sliced and wide WMS: live in-links of the layout, else 0 */
+  uint32_t wsl_slots;     /* sliced WMS: slot words of the layout, padding included; wide WMS:
+                             its 8-byte slots; else 0 */
   uint32_t hop_dist;      /* MS-BFS: the first-hop phase wrote the distance rows (the finalize
                              pass the level rows alone; ORH_HOP_DIST=0 turns it off), else 0 */
+  uint32_t wide_redo;     /* WMS / sliced WMS: the rows the u16 batches flag are redone by the wide
+                             kernel, this many per batch (the sweep could flag rows and the graph
+                             has its wide layout); 0: redone per source (ORH_WMS_WIDE_REDO=0), no
+                             row can be flagged, or another plan */
 } orh_spf_info;
 int orh_last_spf_info(const orh_ctx* ctx, orh_spf_info* out);
 /* device time (HIP events on the context stream) of the last orh_spf_run;

@@ -452,6 +452,7 @@ class SpfSweep {
     d["ms_direct"] = i.ms_direct;
     d["wsl_links"] = i.wsl_links;
     d["wsl_slots"] = i.wsl_slots;
+    d["wide_redo"] = i.wide_redo;
     return d;
   }
   py::tuple fetch(size_t i) {

@@ -90,6 +90,10 @@ struct SpfArgs {
   const uint32_t* wsl_off;   // [slices + 1]
   const uint32_t* wsl_band;  // [waves + 1]
   uint32_t wsl_ovl;
+  // wide multi-source Bellman-Ford (kWmsWide, and the flagged rows of the two
+  // u16 plans): 8-byte slots {u | overloaded(u) << 31, w(u -> v)} in the
+  // geometry of wsl_off / wsl_band (offsets in slots), padding {N, 0}
+  const uint2* wsw_slots;
 };
 
 // phase 2: first-hop masks of the requested rows from the distance rows of
@@ -140,7 +144,8 @@ enum class SpfVariant {
   kRepair,    // ignore-set batch derived from its sources' plain SPFs (whatif_kernels.hip)
   kLdsNh,     // general metrics, labels {dist, first hops} in LDS, first hops fused (no phase 2)
   kWms,       // general metrics, many sources: 4-source Bellman-Ford in LDS, then phase 2
-  kWmsSliced  // the same for any node degree: in-links in a sliced-ELL layout in global memory
+  kWmsSliced, // the same for any node degree: in-links in a sliced-ELL layout in global memory
+  kWmsWide    // the sliced form with u32 labels and full u32 metrics (metrics past 15 bits)
 };
 // spf_wms_kernel: LDS bytes of one batch of `sources` (4 or 8) sources
 // (u16 x sources per node + 1), and the batch width launch_spf_wms takes
@@ -151,15 +156,30 @@ uint32_t wms_sources(uint32_t n_nodes, size_t lds_limit);
 // the u64 spf_lds_nh_kernel (its LDS must fit). Writes dist rows only.
 // wms_k: in-link slots per node of a.wms_slots (4 or 8); a.recs_k: the ELL
 // width of a.recs (for the u64 LDS search of the flagged rows)
-hipError_t launch_spf_wms(SpfArgs a, uint32_t n_rows, uint32_t wms_k, size_t lds_limit, hipStream_t s);
+// wide_block: 0, or the threads per batch of the wide redo (256, 512 or 1,024;
+// a.wsw_slots, a.wsl_off and a.wsl_band of that width set): the flagged rows
+// go to spf_wms_wide_kernel's row-list entry instead
+hipError_t launch_spf_wms(SpfArgs a, uint32_t n_rows, uint32_t wms_k, uint32_t wide_block, size_t lds_limit,
+                          hipStream_t s);
 struct SpfPlan;
 // spf_wms_sliced_kernel: batches of wms_sources rows, `block` threads (256,
 // 512 or 1,024: a.wsl_band holds block / 64 bands); rows whose labels come
 // too close to 16 bits are listed in a.ovf_rows (n_rows + 1 words) and redone
 // by `redo`, the two-phase plan (kDist16 / kDist32) the sweep would run
-// otherwise, whose LDS must fit. Writes dist rows only.
-hipError_t launch_spf_wms_sliced(const SpfPlan& redo, SpfArgs a, uint32_t n_rows, uint32_t block,
+// otherwise, whose LDS must fit - or, wide_redo (a.wsw_slots set), by
+// spf_wms_wide_kernel's row-list entry in batches. Writes dist rows only.
+hipError_t launch_spf_wms_sliced(const SpfPlan& redo, SpfArgs a, uint32_t n_rows, uint32_t block, bool wide_redo,
                                  size_t lds_limit, hipStream_t s);
+// spf_wms_wide_kernel: LDS bytes of one batch of `sources` (4 or 2) sources
+// (u32 x sources per node + 1, and the kernel's static LDS), and the batch
+// width that fits lds_limit: 4, else 2 (or ORH_WMS_WIDE_SOURCES=2), else 0
+size_t wms_wide_lds_bytes(uint32_t n_nodes, uint32_t sources);
+uint32_t wms_wide_sources(uint32_t n_nodes, size_t lds_limit);
+// batches of wms_wide_sources rows, `block` threads (256, 512 or 1,024:
+// a.wsl_band holds block / 64 bands): rows a.order[0, n_rows), or, with
+// a.row_list / a.row_count, the listed rows (a grid for n_rows of them; the
+// count stays on the device). Writes dist rows only, every one final.
+hipError_t launch_spf_wms_wide(SpfArgs a, uint32_t n_rows, uint32_t block, size_t lds_limit, hipStream_t s);
 // spf_lds_nh_kernel: LDS bytes per search (packed: u32 labels, <= 16
 // distinct neighbours per source; else u64 labels)
 size_t lds_nh_bytes(uint32_t n_nodes, bool packed);

@@ -19,6 +19,7 @@ struct LaunchKnobs {
   bool ms_wide;         // ORH_MS_WIDE=1 (opt-in): u64 masks when u32 ones need more than one batch
                         // per CU (see ms_set_width)
   bool wms_four;        // ORH_WMS_SOURCES=4 (A/B): 4-source batches even where 8 fit
+  bool wms_wide_two;    // ORH_WMS_WIDE_SOURCES=2 (A/B): 2-source wide batches even where 4 fit
   bool hop_xcd;         // ORH_HOP_XCD=1 (A/B): first_hop_kernel's XCD-aware source order
   // read once per process
   uint32_t lds16_block;  // ORH_LDS16_BLOCK (A/B): threads per u16 LDS search (one search per CU

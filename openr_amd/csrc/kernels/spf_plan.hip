@@ -38,6 +38,8 @@ LaunchKnobs launch_knobs() {
   k.ms_wide = e && atoi(e) == 1;
   e = getenv("ORH_WMS_SOURCES");
   k.wms_four = e && atoi(e) == 4;
+  e = getenv("ORH_WMS_WIDE_SOURCES");
+  k.wms_wide_two = e && atoi(e) == 2;
   e = getenv("ORH_HOP_XCD");
   k.hop_xcd = e && e[0] == '1';
   return k;

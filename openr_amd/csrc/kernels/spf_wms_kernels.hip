@@ -1,5 +1,6 @@
 // SPF kernels, general metrics, many sources: multi-source Bellman-Ford in
-// LDS (kWms) and its sliced-ELL form for any node degree (kWmsSliced).
+// LDS (kWms), its sliced-ELL form for any node degree (kWmsSliced) and that
+// form with u32 labels for metrics past 15 bits (kWmsWide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,8 +28,9 @@ namespace orh {
 // once before the rounds). First hops: phase 2 over the u32 rows.
 // A label past 0xFFFF - 1 - max metric could hide a distance that does not fit
 // 16 bits: such a batch lists its rows in a.ovf_rows and the caller redoes
-// them (spf_lds_nh_kernel, u64 labels, fused first hops - phase 2 then
-// recomputes the same first hops).
+// them: spf_wms_wide_kernel's row-list entry in batches where the graph has
+// its wide layout, else spf_lds_nh_kernel (u64 labels, fused first hops -
+// phase 2 then recomputes the same first hops).
 constexpr uint32_t kWmsOvl = 0x80000000u;  // slot flag: u is overloaded
 
 // packed u16 pairs: saturating add (v_pk_add_u16 clamp: 0xFFFF stays
@@ -354,6 +356,130 @@ __global__ __launch_bounds__(1024) void spf_wms_sliced_kernel(SpfArgs a) {
   }
 }
 
+// The sliced search with u32 labels (kWmsWide): for graphs whose metrics do
+// not fit the 15 bits of a slot word, and for the rows the two u16 kernels
+// flag. Same geometry (slices, columns, the bands of a.wsl_off / a.wsl_band),
+// same rounds. A node's labels are S u32 (S = 4: 16 B, one ds_read_b128 per
+// in-link, the footprint of the u16 form at 8 sources; S = 2: 8 B, where 16 B
+// per node no longer fit LDS), 0xFFFFFFFF unreached. A slot is 8 bytes, {u |
+// overloaded(u) << 31, w(u -> v)} with the full u32 metric, padding and down
+// links {N, 0}; a wave's column is one coalesced 512-byte load. The add
+// saturates for "unreached + w" alone: the plan is chosen only when
+// wide_metrics(g) is false (orh_api.hip), i.e. the sum of all live metrics
+// plus the largest stays below 0xFFFFFFFF, so no path sum reaches the
+// unreached value and every row this kernel writes is final: no overflow
+// list, no a.wms_limit.
+// Rows: batch b takes rows a.order[b S .. b S + S) of a.n_rows, or, with
+// a.row_list (the flagged rows of a u16 sweep), a.row_list[b S .. b S + S) of
+// *a.row_count; a batch past the count returns before it touches LDS.
+constexpr uint32_t kWmsWideStatic = 16;  // the kernel's static LDS (s_prog), for wms_wide_lds_bytes
+template <int S>
+__global__ __launch_bounds__(1024) void spf_wms_wide_kernel(SpfArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  typedef uint32_t DV __attribute__((ext_vector_type(S)));
+  const uint32_t N = a.n_nodes;
+  const uint32_t tid = threadIdx.x, B = blockDim.x;
+  const uint32_t b0 = blockIdx.x * S;
+  const uint32_t* rows = a.row_list ? a.row_list : a.order;
+  const uint32_t n_rows = a.row_list ? min(*a.row_count, a.n_rows) : a.n_rows;
+  if (b0 >= n_rows) return;
+  const uint32_t nsrc = min(static_cast<uint32_t>(S), n_rows - b0);
+  __shared__ uint32_t s_prog[4];
+  static_assert(sizeof(s_prog) == kWmsWideStatic, "wms_wide_lds_bytes counts the static LDS");
+  DV* D = reinterpret_cast<DV*>(lds);  // [N + 1]; D[N] stays unreached
+  {
+    DV none;
+#pragma unroll
+    for (int q = 0; q < S; ++q) none[q] = kInf;
+    for (uint32_t i = tid; i <= N; i += B) D[i] = none;
+  }
+  if (tid < 3) s_prog[tid] = 0u;
+  __syncthreads();
+  // sources may repeat: each lane of the batch has its own dword
+  if (tid < nsrc) lds[a.dev_of[a.srcs[rows[b0 + tid]]] * S + tid] = 0u;
+  __syncthreads();
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t lane = tid & 63u;
+  const uint32_t sb = a.wsl_band[wave], se = a.wsl_band[wave + 1];
+  const uint2* slots = a.wsw_slots + lane;
+  // an overloaded source reaches its neighbours and no further (as in
+  // spf_wms_kernel): a flagged slot contributes w to the lanes where u is the
+  // source (label 0: only a source holds it, and this pass writes nothing
+  // below 1), once, here. a.wsl_ovl = 0: the layout has no flagged slot
+  if (a.wsl_ovl) {
+    for (uint32_t s = sb; s < se; ++s) {
+      const uint32_t o1 = a.wsl_off[s + 1];
+      const uint32_t v = min(s * 64u + lane, N);
+      for (uint32_t o = a.wsl_off[s]; o < o1; o += 64u) {
+        const uint2 sl = slots[o];
+        if (!(sl.x & kWmsOvl)) continue;
+        const DV du = D[sl.x & ~kWmsOvl];
+        DV d = D[v];  // v < N: a slot of a padding node is never flagged
+#pragma unroll
+        for (int q = 0; q < S; ++q) d[q] = min(d[q], du[q] == 0u ? sl.y : kInf);
+        D[v] = d;
+      }
+    }
+    __syncthreads();
+  }
+  for (uint32_t round = 1;; ++round) {
+    int prog = 0;
+    auto relax = [&](uint32_t s) {
+      const uint32_t o1 = a.wsl_off[s + 1];
+      const uint32_t v = min(s * 64u + lane, N);  // a lane past N: every slot N, never changes
+      const DV own = D[v];
+      DV acc = own;
+      // 4 columns at a time (a slice's width is a multiple of 4): the slot
+      // loads, then the label reads, in flight together
+#pragma unroll 2
+      for (uint32_t o = a.wsl_off[s]; o < o1; o += 256u) {
+        uint2 sl[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sl[k] = slots[o + 64u * k];
+        DV du[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) du[k] = D[(sl[k].x & kWmsOvl) ? N : sl[k].x];  // dead after the pass above
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          DV w;  // padding: w = 0 on the unreached entry
+#pragma unroll
+          for (int q = 0; q < S; ++q) w[q] = sl[k].y;
+          acc = __builtin_elementwise_min(acc, __builtin_elementwise_add_sat(du[k], w));
+        }
+      }
+      bool changed = false;
+#pragma unroll
+      for (int q = 0; q < S; ++q) changed |= acc[q] != own[q];
+      if (changed) {
+        D[v] = acc;
+        prog = 1;
+      }
+    };
+    // forward, then back (the last slice was relaxed just now): a band passes
+    // its changes both ways in one round
+    for (uint32_t s = sb; s < se; ++s) relax(s);
+    if (se > sb)
+      for (uint32_t s = se - 1; s-- > sb;) relax(s);
+    if (prog) s_prog[round % 3u] = 1u;
+    lds_barrier();
+    if (!s_prog[round % 3u]) break;
+    if (tid == 0) s_prog[(round + 2u) % 3u] = 0u;
+  }
+  // rows out in host order; the unreached label is the rows' kInf already
+  uint32_t* out[S];
+#pragma unroll
+  for (int k = 0; k < S; ++k)
+    out[k] = static_cast<uint32_t>(k) < nsrc ? dist_row(a.out_dist, a.scratch, a.n_out, N, rows[b0 + k]) : nullptr;
+  for (uint32_t i = tid; i < N; i += B) {
+    const DV d = D[a.dev_of[i]];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      if (static_cast<uint32_t>(k) >= nsrc) break;
+      __builtin_nontemporal_store(d[k], &out[k][i]);
+    }
+  }
+}
+
 size_t wms_lds_bytes(uint32_t n_nodes, uint32_t sources) {
   const size_t cw = (static_cast<size_t>(n_nodes) + 63) / 64 / 32 + 1;
   return (static_cast<size_t>(n_nodes) + 1) * 2 * sources + 3 * cw * 4;  // labels, then the chunk-change bitmaps
@@ -388,7 +514,39 @@ uint32_t wms_sources(uint32_t n_nodes, size_t lds_limit) {
   return !launch_knobs().wms_four && n_nodes <= 10240 && wms_lds_bytes(n_nodes, 8) <= lds_limit ? 8u : 4u;
 }
 
-hipError_t launch_spf_wms(SpfArgs a, uint32_t n_rows, uint32_t wms_k, size_t lds_limit, hipStream_t s) {
+size_t wms_wide_lds_bytes(uint32_t n_nodes, uint32_t sources) {
+  return (static_cast<size_t>(n_nodes) + 1) * 4 * sources + kWmsWideStatic;
+}
+
+uint32_t wms_wide_sources(uint32_t n_nodes, size_t lds_limit) {
+  if (n_nodes == 0 || n_nodes > 20480) return 0u;
+  if (!launch_knobs().wms_wide_two && wms_wide_lds_bytes(n_nodes, 4) <= lds_limit) return 4u;
+  return wms_wide_lds_bytes(n_nodes, 2) <= lds_limit ? 2u : 0u;
+}
+
+hipError_t launch_spf_wms_wide(SpfArgs a, uint32_t n_rows, uint32_t block, size_t lds_limit, hipStream_t s) {
+  if (n_rows == 0) return hipSuccess;
+  const uint32_t S = wms_wide_sources(a.n_nodes, lds_limit);
+  if (!S || !a.wsw_slots || !a.wsl_off || !a.wsl_band || !a.dev_of || (!a.row_list != !a.row_count) ||
+      (block != 256 && block != 512 && block != 1024))
+    return hipErrorInvalidValue;
+  a.n_rows = n_rows;
+  const uint32_t batches = (n_rows + S - 1) / S;
+  const size_t lds = wms_wide_lds_bytes(a.n_nodes, S) - kWmsWideStatic;
+  return S == 4 ? launch(spf_wms_wide_kernel<4>, a, batches, block, lds, s)
+                : launch(spf_wms_wide_kernel<2>, a, batches, block, lds, s);
+}
+
+// the rows a u16 sweep flagged (a.ovf_rows: count, then rows), redone in wide
+// batches: a grid for every row, the batches past the count exit at once
+static hipError_t redo_wide(SpfArgs a, uint32_t n_rows, uint32_t block, size_t lds_limit, hipStream_t s) {
+  a.row_list = a.ovf_rows + 1;
+  a.row_count = a.ovf_rows;
+  return launch_spf_wms_wide(a, n_rows, block, lds_limit, s);
+}
+
+hipError_t launch_spf_wms(SpfArgs a, uint32_t n_rows, uint32_t wms_k, uint32_t wide_block, size_t lds_limit,
+                          hipStream_t s) {
   if (n_rows == 0) return hipSuccess;
   if (!a.ovf_rows || !a.wms_slots || a.n_nodes > 20480 || a.n_nodes >= 0xFFFFu) return hipErrorInvalidValue;
   a.n_rows = n_rows;
@@ -406,15 +564,17 @@ hipError_t launch_spf_wms(SpfArgs a, uint32_t n_rows, uint32_t wms_k, size_t lds
   else
     e = wms_k == 8 ? launch_wms_k<8, 4>(a, batches, lds, s) : launch_wms_k<4, 4>(a, batches, lds, s);
   if (e != hipSuccess) return e;
-  // rows whose distances may not fit 16 bits: the u64 LDS search over the
-  // list (workgroups past its length exit at once); its first-hop rows are
+  // rows whose distances may not fit 16 bits: wide batches over the list
+  // (wide_block: the graph has its wide layout), or the u64 LDS search
+  // (workgroups past its length exit at once); its first-hop rows are
   // rewritten, identically, by phase 2
+  if (wide_block) return redo_wide(a, n_rows, wide_block, lds_limit, s);
   a.row_list = a.ovf_rows + 1;
   a.row_count = a.ovf_rows;
   return launch_lds_nh_rows(a, n_rows, s);
 }
 
-hipError_t launch_spf_wms_sliced(const SpfPlan& redo, SpfArgs a, uint32_t n_rows, uint32_t block,
+hipError_t launch_spf_wms_sliced(const SpfPlan& redo, SpfArgs a, uint32_t n_rows, uint32_t block, bool wide_redo,
                                  size_t lds_limit, hipStream_t s) {
   if (n_rows == 0) return hipSuccess;
   if (!a.ovf_rows || !a.wsl_slots || !a.wsl_off || !a.wsl_band || a.n_nodes > 20480 ||
@@ -432,9 +592,11 @@ hipError_t launch_spf_wms_sliced(const SpfPlan& redo, SpfArgs a, uint32_t n_rows
   e = S == 8 ? launch(spf_wms_sliced_kernel<8>, a, batches, block, lds, s)
              : launch(spf_wms_sliced_kernel<4>, a, batches, block, lds, s);
   if (e != hipSuccess) return e;
-  // rows whose distances may not fit 16 bits: the two-phase plan's own search
-  // (distances only, any neighbour count) over the list; workgroups past its
-  // length exit at once
+  // rows whose distances may not fit 16 bits: wide batches over the list
+  // (wide_redo: the layout carries its 8-byte slots too), or the two-phase
+  // plan's own search (distances only, any neighbour count); workgroups past
+  // the list's length exit at once
+  if (wide_redo) return redo_wide(a, n_rows, block, lds_limit, s);
   a.row_list = a.ovf_rows + 1;
   a.row_count = a.ovf_rows;
   return launch_spf(redo, a, n_rows, s);

@@ -146,16 +146,20 @@ struct orh_graph {
   uint32_t* d_wms = nullptr;
   bool wms_dirty = true, wms_ok = false;
   uint32_t wms_maxw = 0, wms_k = 4;
+  uint32_t wms_maxdeg = 0;  // largest CSR row, as of the last sync_wms_layout
   // sliced multi-source Bellman-Ford (kWmsSliced): the same slot words for
   // any degree, column-major per 64-node slice (sync_wms_sliced_layout).
   // d_wsl: slots | slice offsets [slices + 1] | band starts for 4, 8 and 16
-  // waves (5 + 9 + 17 words); wsl_ok: N <= 20,480 and live metrics 1..0x7FFF
+  // waves (5 + 9 + 17 words) | the 8-byte slots of the wide kernel
+  // (kWmsWide), when asked for; wsl_ok: N <= 20,480 and live metrics
+  // 1..0x7FFF; wsl_wide: the 8-byte slots are there (N <= 20,480, live
+  // metrics >= 1); wsl_maxw: the largest live metric
   uint32_t* d_wsl = nullptr;
   size_t d_wsl_cap = 0;  // in u32
-  bool wsl_dirty = true, wsl_ok = false, wsl_ovl = false;
+  bool wsl_dirty = true, wsl_ok = false, wsl_ovl = false, wsl_wide = false;
   uint32_t wsl_maxw = 0, wsl_block = 1024;
-  size_t wsl_off_at = 0, wsl_band_at = 0;  // word offsets into d_wsl
-  uint32_t wsl_real = 0, wsl_padded = 0;   // live in-links, slot words
+  size_t wsl_off_at = 0, wsl_band_at = 0, wsl_wide_at = 0;  // word offsets into d_wsl
+  uint32_t wsl_real = 0, wsl_padded = 0;   // live in-links, slots (padding included)
   std::vector<int32_t> row_of;  // scratch for orh_spf_run (all -1 between calls)
   // orh_spf_run's staged request on this graph (sources, ignore sets,
   // neighbour rows, batch order), keyed by the request: a repeated sweep
@@ -427,6 +431,7 @@ int sync_wms_layout(orh_graph* g) {
   for (uint32_t v = 0; v < N; ++v) maxdeg = std::max(maxdeg, g->row_ptr[v + 1] - g->row_ptr[v]);
   const uint32_t K = maxdeg <= 4 ? 4u : 8u;  // slots per node (its own width, not the ELL's)
   g->wms_k = K;
+  g->wms_maxdeg = maxdeg;
   g->wms_ok = N > 0 && N <= 20480 && maxdeg <= 8;
   g->wms_maxw = 0;
   std::vector<uint32_t> slots;
@@ -466,40 +471,51 @@ int sync_wms_layout(orh_graph* g) {
 // slices: band starts for 4, 8 and 16 waves, cut where the running column
 // count (+ 1 per slice, its own label) passes w / waves of the total.
 // wsl_block: the widest workgroup that still cuts the heaviest band by a
-// tenth against half as many waves (one indivisible wide slice bounds it)
-int sync_wms_sliced_layout(orh_graph* g) {
-  if (!g->wsl_dirty) return ORH_OK;
+// tenth against half as many waves (one indivisible wide slice bounds it).
+// wide: the 8-byte slots of spf_wms_wide_kernel too, {u | overloaded(u) << 31,
+// w} with the full metric, padding {N, 0}, in the same slices, columns and
+// bands (one set of offsets serves both slot arrays); a graph whose metrics
+// pass 15 bits has these alone (wsl_ok false, wsl_wide true)
+int sync_wms_sliced_layout(orh_graph* g, bool wide) {
+  if (!g->wsl_dirty && (!wide || g->wsl_wide)) return ORH_OK;
   int rc = sync_ms_layout(g);
   if (rc) return rc;
   const uint32_t N = g->n_nodes;
-  g->wsl_ok = N > 0 && N <= 20480;
+  bool shape_ok = N > 0 && N <= 20480;  // and no zero metric: what both slot formats need
   g->wsl_maxw = 0;
   g->wsl_ovl = false;
+  g->wsl_wide = false;
   g->wsl_real = g->wsl_padded = 0;
   const uint32_t n_slice = (N + 63) / 64;
   std::vector<uint32_t> off(n_slice + 1, 0), deg(N, 0);
-  for (uint32_t dv = 0; dv < N && g->wsl_ok; ++dv) {
+  for (uint32_t dv = 0; dv < N && shape_ok; ++dv) {
     const uint32_t v = g->ms_host_of[dv];
     for (uint32_t e = g->row_ptr[v]; e < g->row_ptr[v + 1]; ++e) {
       if (g->meta[e] & ORH_META_DOWN) continue;
       const uint32_t w = g->w_in[e];
-      if (w == 0 || w > 0x7FFFu) {
-        g->wsl_ok = false;
+      if (w == 0) {
+        shape_ok = false;
         break;
       }
       g->wsl_maxw = std::max(g->wsl_maxw, w);
       ++deg[dv];
     }
   }
-  if (g->wsl_ok) {
+  g->wsl_ok = shape_ok && g->wsl_maxw <= 0x7FFFu;
+  wide = wide && shape_ok;
+  if (g->wsl_ok || wide) {
     for (uint32_t s = 0; s < n_slice; ++s) {
       uint32_t width = 0;
       for (uint32_t dv = s * 64; dv < std::min(N, s * 64 + 64); ++dv) width = std::max(width, deg[dv]);
       off[s + 1] = off[s] + ((width + 3u) & ~3u) * 64u;
     }
     const size_t n_slots = off[n_slice];
-    const size_t off_at = n_slots, band_at = off_at + n_slice + 1, total = band_at + 5 + 9 + 17;
+    const size_t off_at = n_slots, band_at = off_at + n_slice + 1;
+    const size_t wide_at = (band_at + 5 + 9 + 17 + 1) & ~size_t{1};  // 8-byte aligned
+    const size_t total = wide_at + (wide ? 2 * n_slots : 0);
     std::vector<uint32_t> st(total, N);
+    if (wide)  // padding {N, 0}
+      for (size_t i = 0; i < n_slots; ++i) st[wide_at + 2 * i + 1] = 0u;
     for (uint32_t dv = 0; dv < N; ++dv) {
       const uint32_t v = g->ms_host_of[dv];
       uint32_t k = 0;
@@ -507,12 +523,19 @@ int sync_wms_sliced_layout(orh_graph* g) {
         if (g->meta[e] & ORH_META_DOWN) continue;
         const uint32_t u = g->col[e];
         if (g->overloaded[u]) g->wsl_ovl = true;
-        st[off[dv / 64] + 64u * k++ + (dv & 63u)] =
-            g->ms_dev_of[u] | (g->w_in[e] << 16) | (g->overloaded[u] ? 0x80000000u : 0u);
+        const size_t at = off[dv / 64] + 64u * k++ + (dv & 63u);
+        const uint32_t uw = g->ms_dev_of[u] | (g->overloaded[u] ? 0x80000000u : 0u);
+        if (g->wsl_ok) st[at] = uw | (g->w_in[e] << 16);
+        if (wide) {
+          st[wide_at + 2 * at] = uw;
+          st[wide_at + 2 * at + 1] = g->w_in[e];
+        }
         ++g->wsl_real;
       }
     }
     g->wsl_padded = static_cast<uint32_t>(n_slots);
+    g->wsl_wide = wide;
+    g->wsl_wide_at = wide_at;
     std::copy(off.begin(), off.end(), st.begin() + off_at);
     uint64_t all = 0;
     for (uint32_t s = 0; s < n_slice; ++s) all += (off[s + 1] - off[s]) / 64 + 1;
@@ -2201,6 +2224,12 @@ struct SpfKnobs {
   // ORH_WMS_SLICED_BLOCK=256|512|1024: threads per kWmsSliced batch instead of
   // the layout's choice (0) (A/B)
   uint32_t wms_sliced_block;
+  // ORH_WMS_WIDE=0: no kWmsWide plan (A/B): sweeps whose metrics pass 15 bits
+  // keep the per-source plans
+  bool wms_wide;
+  // ORH_WMS_WIDE_REDO=0: the rows kWms / kWmsSliced flag are redone per source
+  // instead of in wide batches (A/B)
+  bool wms_wide_redo;
   // ORH_MS_DIRECT=0: the rows of a host-order multi-source BFS through ms_lvl
   // and ms_finalize instead of out of the search kernel (A/B)
   bool ms_direct;
@@ -2237,6 +2266,8 @@ SpfKnobs spf_knobs(const orh_ctx* ctx) {
   k.wms_sliced_all = env_is("ORH_WMS_SLICED_ALL", '1');
   const int b = env_int("ORH_WMS_SLICED_BLOCK", 0);
   k.wms_sliced_block = (b == 256 || b == 512 || b == 1024) ? static_cast<uint32_t>(b) : 0u;
+  k.wms_wide = !env_is("ORH_WMS_WIDE", '0');
+  k.wms_wide_redo = !env_is("ORH_WMS_WIDE_REDO", '0');
   k.ms_direct = !env_is("ORH_MS_DIRECT", '0');
   k.wms_skip = env_is("ORH_WMS_SKIP", '1');
   k.wms_band = !env_is("ORH_WMS_BAND", '0');
@@ -2249,6 +2280,8 @@ struct SweepPlan {
   orh::SpfPlan run;    // the search
   uint32_t n_rows;     // rows it searches: the staged ones, or one per source when the first hops are fused
   bool wms, wsl;       // kWms; kWmsSliced (whose flagged rows the base plan's search redoes)
+  bool wide;           // kWmsWide
+  uint32_t wide_redo;  // kWms / kWmsSliced: sources per wide batch that redoes the flagged rows (0: per source)
   bool lds_nh_packed;  // kLdsNh with u32 labels first
   bool fused;          // the search writes the first hops too: no phase 2
   size_t label_words;  // d_labels entries to reserve (0: none)
@@ -2267,6 +2300,7 @@ uint32_t block_by_sources(const orh_ctx* ctx, uint32_t n_src) {
 //   kBfsNh      BFS base, at most bfs_nh_max sources
 //   kWms        many sources on a graph whose in-links fit 8 slots per node
 //   kWmsSliced  the same sweep where kWms declined
+//   kWmsWide    the same sweep where those two declined for a metric past 15 bits alone
 //   kLdsNh      general metrics otherwise, sources of at most 32 neighbours
 //   kGlobalNh   HBM base
 int choose_plan(orh_graph* g, const orh::SpfPlan& base, const SweepFacts& f, const SpfKnobs& k,
@@ -2300,24 +2334,52 @@ int choose_plan(orh_graph* g, const orh::SpfPlan& base, const SweepFacts& f, con
   // many sources: multi-source Bellman-Ford batches in LDS, then the first
   // hops over the u32 rows (phase 2)
   const bool many = weighted && !f.has_ign && f.n_src >= k.wms_min && orh::wms_lds_bytes(N) <= ctx->lds_limit;
+  // u32 labels: sources per wide batch that fit LDS (0: none); big: some live
+  // metric is past the 15 bits of a u16 plan's slot word; may_flag: a u16
+  // label can pass 0xFFFE - max metric, so a u16 sweep may flag rows
+  const uint32_t wide_s = many ? orh::wms_wide_sources(N, ctx->lds_limit) : 0u;
+  const bool big = g->max_metric > 0x7FFFu;
+  const bool may_flag = g->sum_max_metric / 2 + 2 * static_cast<uint64_t>(g->max_metric) > 0xFFFEull;
+  const bool redo_wide = k.wms_wide_redo && wide_s && !big && may_flag;
+  bool wms_shape = false;  // kWms's graph but for the metric range: every degree <= 8
   if (many && k.wms && lds_nh_fits) {  // spf_wms_kernel; flagged rows redone by the u64 LDS search
     int rc = sync_wms_layout(g);
     if (rc) return rc;
     p.wms = g->wms_ok;
+    wms_shape = g->wms_maxdeg <= 8;
   }
   // a graph kWms declined, with sources of more than 32 distinct neighbours
   // (where kLdsNh does not apply and the sweep would run the two-phase plan):
   // spf_wms_sliced_kernel, flagged rows redone by that plan's own search
-  if (many && !p.wms && k.wms_sliced && base.lds_bytes <= ctx->lds_limit &&
-      (f.max_nbr > 32 || k.wms_sliced_all)) {
-    int rc = sync_wms_sliced_layout(g);
+  const bool wsl_shape = many && !p.wms && k.wms_sliced && base.lds_bytes <= ctx->lds_limit &&
+                         (f.max_nbr > 32 || k.wms_sliced_all);
+  const bool wide_rule = many && !p.wms && k.wms_wide && wide_s && big && (wms_shape || wsl_shape);
+  if (wsl_shape) {
+    int rc = sync_wms_sliced_layout(g, redo_wide || wide_rule);
     if (rc) return rc;
     p.wsl = g->wsl_ok;
   }
-  if (p.wms || p.wsl) {
+  // a sweep the two u16 plans declined for their metric range alone:
+  // spf_wms_wide_kernel, u32 labels and full metrics, every row final
+  if (wide_rule && !p.wsl) {
+    int rc = sync_wms_sliced_layout(g, true);
+    if (rc) return rc;
+    p.wide = g->wsl_wide && g->wsl_maxw > 0x7FFFu;
+  }
+  // the rows a u16 sweep flags: redone in wide batches where the graph has
+  // its wide layout, else per source
+  if ((p.wms || p.wsl) && redo_wide) {
+    int rc = sync_wms_sliced_layout(g, true);
+    if (rc) return rc;
+    if (g->wsl_wide) p.wide_redo = wide_s;
+  }
+  if (p.wide) {
+    p.run.variant = V::kWmsWide;
+    p.wsl_block = k.wms_sliced_block ? k.wms_sliced_block : g->wsl_block;
+  } else if (p.wms || p.wsl) {
     p.run.variant = p.wms ? V::kWms : V::kWmsSliced;
     p.label_words = (static_cast<size_t>(p.n_rows) + 2) / 2 + 1;  // the overflow row list
-    if (p.wsl) p.wsl_block = k.wms_sliced_block ? k.wms_sliced_block : g->wsl_block;
+    if (p.wsl || p.wide_redo) p.wsl_block = k.wms_sliced_block ? k.wms_sliced_block : g->wsl_block;
   } else if (weighted && k.lds_nh && (f.has_ign || f.n_src >= k.lds_nh_min) && f.max_nbr <= 32 && lds_nh_fits) {
     // one search per source with the first hops fused (spf_lds_nh_kernel)
     // instead of the two-phase LDS kernels, which also search every neighbour
@@ -2410,6 +2472,13 @@ int fill_spf_args(orh_graph* g, const SweepFacts& f, const SweepPlan& sp, const 
     a.wsl_ovl = g->wsl_ovl ? 1u : 0u;
     a.wsl_band = g->d_wsl + g->wsl_band_at + (sp.wsl_block == 256 ? 0u : sp.wsl_block == 512 ? 5u : 14u);
   }
+  if (sp.wide || sp.wide_redo) {  // the wide kernel's slots in the sliced geometry
+    a.dev_of = g->d_ms_dev_of;
+    a.wsw_slots = reinterpret_cast<const uint2*>(g->d_wsl + g->wsl_wide_at);
+    a.wsl_off = g->d_wsl + g->wsl_off_at;
+    a.wsl_ovl = g->wsl_ovl ? 1u : 0u;
+    a.wsl_band = g->d_wsl + g->wsl_band_at + (sp.wsl_block == 256 ? 0u : sp.wsl_block == 512 ? 5u : 14u);
+  }
   if (sp.wms) {
     a.dev_of = g->d_ms_dev_of;
     a.wms_slots = g->d_wms;
@@ -2473,7 +2542,8 @@ std::string plan_text(const SweepPlan& sp, bool shape) {
   return m;
 }
 
-// the search; kWmsSliced redoes its flagged rows with the base plan's search
+// the search; kWmsSliced redoes its flagged rows with the base plan's search,
+// or, like kWms, in wide batches (sp.wide_redo)
 int launch_phase1(orh_graph* g, const orh::SpfPlan& base, const SweepPlan& sp, const orh::SpfArgs& a) {
   using V = orh::SpfVariant;
   orh_ctx* ctx = g->ctx;
@@ -2483,8 +2553,11 @@ int launch_phase1(orh_graph* g, const orh::SpfPlan& base, const SweepPlan& sp, c
   const hipError_t e =
       sp.run.variant == V::kLdsNh
           ? orh::launch_spf_lds_nh(a, sp.n_rows, g->ell_k, sp.lds_nh_packed, sp.run.block, ctx->stream)
-      : sp.wms ? orh::launch_spf_wms(a, sp.n_rows, g->wms_k, ctx->lds_limit, ctx->stream)
-      : sp.wsl ? orh::launch_spf_wms_sliced(base, a, sp.n_rows, sp.wsl_block, ctx->lds_limit, ctx->stream)
+      : sp.wide ? orh::launch_spf_wms_wide(a, sp.n_rows, sp.wsl_block, ctx->lds_limit, ctx->stream)
+      : sp.wms  ? orh::launch_spf_wms(a, sp.n_rows, g->wms_k, sp.wide_redo ? sp.wsl_block : 0u, ctx->lds_limit,
+                                      ctx->stream)
+      : sp.wsl  ? orh::launch_spf_wms_sliced(base, a, sp.n_rows, sp.wsl_block, sp.wide_redo != 0, ctx->lds_limit,
+                                             ctx->stream)
                : orh::launch_spf(sp.run, a, sp.n_rows, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, ("spf kernel launch " + plan_text(sp, true)).c_str());
   return ORH_OK;
@@ -2551,13 +2624,20 @@ orh_spf_info search_info(const orh_graph* g, const SweepPlan& sp, const orh::Spf
   info.batch_sources = ms ? sp.run.ms_width : 0;
   info.ms_threads = ms ? sp.run.block : 0;
   info.ms_skip = ms && a.ms_bw ? 1u : 0u;
-  info.ms_direct = ms ? a.ms_direct : (sp.wms || sp.wsl) && g->ms_identity ? 1u : 0u;
+  info.ms_direct = ms ? a.ms_direct : (sp.wms || sp.wsl || sp.wide) && g->ms_identity ? 1u : 0u;
   if (sp.wsl) {
     info.batch_sources = orh::wms_sources(g->n_nodes, g->ctx->lds_limit);
     info.ms_threads = sp.wsl_block;
     info.wsl_links = g->wsl_real;
     info.wsl_slots = g->wsl_padded;
   }
+  if (sp.wide) {
+    info.batch_sources = orh::wms_wide_sources(g->n_nodes, g->ctx->lds_limit);
+    info.ms_threads = sp.wsl_block;
+    info.wsl_links = g->wsl_real;
+    info.wsl_slots = g->wsl_padded;
+  }
+  info.wide_redo = sp.wide_redo;
   return info;
 }
 

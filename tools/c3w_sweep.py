@@ -56,7 +56,8 @@ def degree_graph(n, seed, max_metric=64):
     return [create_adj_db(f"n{i}", adjs[i], i + 1, False, K_TESTING_AREA) for i in range(n)]
 
 
-def ab(hip, oracle_mod, dbs, reps, check_rows, threads):
+def ab(hip, oracle_mod, dbs, reps, check_rows, threads, knob="ORH_WMS_SLICED"):
+    """The A/B of one per-run knob (1 against 0) on the all-sources sweep of dbs."""
     from helpers import row_digest
     from openr_amd.facade import Backend, load_topology
     from openr_amd.types import K_TESTING_AREA as A
@@ -66,12 +67,12 @@ def ab(hip, oracle_mod, dbs, reps, check_rows, threads):
     sw = ls.sweep(names, True)
     plans = {"0": {"ms": [], "ph": []}, "1": {"ms": [], "ph": []}}
     for flag in ("0", "1"):  # warm-up: layouts, staging, kernel attributes
-        os.environ["ORH_WMS_SLICED"] = flag
+        os.environ[knob] = flag
         sw.run()
         sw.sync()
     for _ in range(reps):
         for flag in ("0", "1"):
-            os.environ["ORH_WMS_SLICED"] = flag
+            os.environ[knob] = flag
             sw.run()
             plans[flag]["ms"].append(sw.last_ms())
             plans[flag]["ph"].append(sw.phase_ms())
@@ -86,7 +87,7 @@ def ab(hip, oracle_mod, dbs, reps, check_rows, threads):
         rows = sorted(random.Random(5).sample(rows, check_rows))
     out = {}
     for flag in ("0", "1"):
-        os.environ["ORH_WMS_SLICED"] = flag
+        os.environ[knob] = flag
         sw.run()
         sw.sync()
         bad = 0
@@ -105,7 +106,7 @@ def ab(hip, oracle_mod, dbs, reps, check_rows, threads):
                           "max": round(max(p["ms"]), 4)},
             "phase_ms": [round(statistics.median(x[i] for x in p["ph"]), 4) for i in (0, 1)],
             "info": p["info"], "rows_checked": len(rows), "digest_mismatches": bad}
-    os.environ.pop("ORH_WMS_SLICED", None)
+    os.environ.pop(knob, None)
     si = out["sliced"]["info"]
     out["nodes"], out["sources"], out["reps"] = sw.nodes, len(names), reps
     out["padded_to_real_slots"] = round(si["wsl_slots"] / si["wsl_links"], 3) if si.get("wsl_links") else None
