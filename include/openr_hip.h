@@ -260,6 +260,13 @@ int orh_graph_info(const orh_graph* g, uint32_t* n_nodes, uint32_t* n_edges);
 /* device array of the graph's node overload flags (u8 [n_nodes]), valid
  * until the next orh_graph_load (route selection's drained-node filter) */
 int orh_graph_device_flags(const orh_graph* g, const uint8_t** d_overloaded);
+/* the node order of the multi-source BFS layout: h_out[i] (i < min(n_nodes,
+ * cap)) is the node with device id i; *kind (optional) says which order the
+ * graph took at its load (ORH_MS_ORDER=cluster|cm|host, else by depth) */
+#define ORH_MS_ORDER_CM 0u      /* Cuthill-McKee */
+#define ORH_MS_ORDER_HOST 1u    /* the node ids themselves */
+#define ORH_MS_ORDER_CLUSTER 2u /* runs of 64 ids that are compact BFS clusters */
+int orh_graph_ms_order(const orh_graph* g, uint32_t* h_out, uint32_t cap, uint32_t* kind);
 /* distinct neighbour node ids of src in ascending order (bit k of an nh
  * mask is h_out[k]); *n_out receives the count even if it exceeds cap */
 int orh_graph_neighbors(const orh_graph* g, uint32_t src, uint32_t* h_out, uint32_t cap,

@@ -16,6 +16,7 @@
 #include "rib_policy.h"
 #include "spf_solver.h"
 #include "decision_ingest.h"
+#include "ms_order.h"
 #include "multi_device.h"
 #include "thrift_compact.h"
 
@@ -635,6 +636,25 @@ struct RibStatementProbe {  // a lone RibPolicyStatement (RibPolicyTest.cpp stat
 PYBIND11_MODULE(_openr_host, m) {
   m.doc() = "OpenR Decision SPF / route build on MI355X (host library over libopenr_hip)";
 
+  // the node orders of the multi-source layouts (ms_order.h; no device): for
+  // distinct-neighbour lists in ascending id, (Cuthill-McKee order, its BFS
+  // depth, cluster order), each order as node per device id
+  m.def("ms_orders", [](const std::vector<std::vector<uint32_t>>& adj) {
+    const uint32_t n = static_cast<uint32_t>(adj.size());
+    std::vector<uint32_t> ptr(n + 1, 0), dn;
+    for (uint32_t v = 0; v < n; ++v) {
+      for (uint32_t u : adj[v]) {
+        if (u >= n) throw std::invalid_argument("ms_orders: neighbour id out of range");
+        dn.push_back(u);
+      }
+      ptr[v + 1] = static_cast<uint32_t>(dn.size());
+    }
+    std::vector<uint32_t> cmHost, cmDev, clHost, clDev;
+    const uint32_t depth = orh::ms_cm_order(n, ptr.data(), dn.data(), cmHost, cmDev);
+    orh::ms_cluster_order(n, ptr.data(), dn.data(), cmHost.data(), cmDev.data(), clHost, clDev);
+    return py::make_tuple(cmHost, depth, clHost);
+  });
+
   py::class_<LinkState>(m, "LinkState")
       .def("update_adjacency_database",
            [](LinkState& s, py::tuple db, uint64_t up, uint64_t down) {
@@ -809,6 +829,19 @@ PYBIND11_MODULE(_openr_host, m) {
              std::vector<std::string> out;
              for (uint32_t v : ids) out.push_back(s.nodeName(v));
              return out;
+           })
+      .def("ms_order",  // (kind, node names by device id) of the multi-source BFS layout
+           [](const LinkState& s) {
+             orh_graph* g = s.deviceGraph();
+             uint32_t n = 0, kind = 0;
+             orh_graph_info(g, &n, nullptr);
+             std::vector<uint32_t> ids(n);
+             if (orh_graph_ms_order(g, ids.data(), n, &kind) != ORH_OK)
+               throw std::runtime_error(std::string("orh_graph_ms_order: ") + orh_last_error(s.context()));
+             std::vector<std::string> names;
+             for (uint32_t v : ids) names.push_back(s.nodeName(v));
+             static const char* const kKinds[] = {"cm", "host", "cluster"};
+             return py::make_tuple(std::string(kKinds[kind < 3 ? kind : 0]), names);
            })
       .def("node_names",
            [](const LinkState& s) {

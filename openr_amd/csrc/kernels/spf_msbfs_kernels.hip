@@ -17,7 +17,8 @@ namespace orh {
 // bit per source (multi-source BFS, Then et al., VLDB 2015), as a pull over
 // the nodes:
 //   nx(v) = (OR over live records v -> u of F(u)) & ~visited(v)
-// Thread t owns the Cuthill-McKee nodes t, t + B, ..., t + (J-1)B and keeps
+// Thread t owns the nodes t, t + B, ..., t + (J-1)B of the layout's order
+// (cluster order on deep graphs, else Cuthill-McKee: host/ms_order.h) and keeps
 // their ELL columns (packed 16-bit; a dead or down slot points at an
 // always-zero LDS entry) and their visited masks in registers, so LDS holds
 // only the two frontier arrays (this level's and the next): 8 bytes per node
@@ -39,8 +40,9 @@ namespace orh {
 // >= 254 are written to the output row directly (marker 254), so any depth is
 // exact; 255 = unreached.
 //
-// Interval skip (kSkip): nodes are numbered in Cuthill-McKee order, so every
-// live record v -> u has |u - v| <= bw (the layout's bandwidth). If the nodes
+// Interval skip (kSkip): every live record v -> u has |u - v| <= bw, the
+// bandwidth of the layout's order (small in Cuthill-McKee order, which is
+// where the skip can pay; most of N in cluster order). If the nodes
 // that gained a bit at level L-1 span the ids [lo, hi], only nodes in
 // [lo - bw, hi + bw] can gain one at level L; a 64-node slice (one wave's
 // nodes of one j) outside it is skipped without reading its neighbours'
@@ -375,6 +377,9 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
         for (uint32_t u = 0; u < 8; ++u) {
           uint8_t* nb = blk + ((static_cast<uint32_t>(x[u]) >> 8) & 0x7FFu) * kP;  // (j * 64 + lane) * kP
           const uint8_t lv = static_cast<uint8_t>(x[u] & 0xFFu);
+          // (the first two bits of an event decoded straight-line ahead of this
+          // loop: 19.49 against 19.56 ms per step in cluster order, inside the
+          // run-to-run range - profiles/ms_cluster/step_ab.txt)
           for (V q = static_cast<V>(x[u] >> 32); q; q &= q - 1) nb[MsMask<M>::ctz(q)] = lv;
         }
       }

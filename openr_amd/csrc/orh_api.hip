@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/openr_hip.h"
+#include "host/ms_order.h"
 #include "kernels/ksp_kernels.h"
 #include "kernels/route_kernels.h"
 #include "kernels/spf_kernels.h"
@@ -94,7 +95,7 @@ struct orh_ctx {
 struct StagedRequest {
   std::vector<uint32_t> key;  // graph generation + sources + ignore sets; empty: nothing staged
   uint32_t n_rows = 0;        // sources + neighbour rows
-  uint32_t off_ign_ptr = 0, off_ign = 0, off_nbr_ptr = 0, off_nbr_row = 0, off_order = 0;
+  uint32_t off_ign_ptr = 0, off_ign = 0, off_nbr_ptr = 0, off_nbr_row = 0, off_order = 0, off_order_ms = 0;
   uint32_t xcd_group = 0;  // HopArgs::xcd_group
 };
 
@@ -128,9 +129,10 @@ struct orh_graph {
   uint32_t* d_link = nullptr;
   uint16_t* d_rank_out = nullptr;
   uint8_t* d_ovl = nullptr;
-  // multi-source BFS layout: the same ELL records in a Cuthill-McKee node
+  // multi-source layouts: the same ELL records in a Cuthill-McKee node
   // order (neighbours get nearby ids, so a batch of consecutive sources is a
-  // compact region and a wave's 64 nodes progress together). Rebuilt lazily
+  // compact region and a wave's 64 nodes progress together); the BFS of a
+  // deep graph has an order of its own (msb_*, below). Rebuilt lazily
   // after attribute patches. Rows in HBM are always indexed by host id.
   std::vector<uint32_t> ms_dev_of, ms_host_of;  // host -> CM id, CM id -> host
   bool ms_identity = false;  // the layout kept the host order (order_nodes)
@@ -140,6 +142,18 @@ struct orh_graph {
   uint2* d_ms_recs = nullptr;
   uint32_t* d_ms_dev_of = nullptr;
   uint32_t* d_ms_host_of = nullptr;
+  // the multi-source BFS's own node order (ms_cluster_order, host/ms_order.h):
+  // runs of 64 ids that are compact clusters. ms_cluster: the graph has one
+  // (order_nodes decides); then ms_recs, the BFS batches and the BFS kernels'
+  // id maps use msb_*, while the multi-source Bellman-Ford layouts, whose
+  // band cuts lean on Cuthill-McKee's band structure, keep ms_dev_of /
+  // ms_host_of. Without it the BFS shares those
+  std::vector<uint32_t> msb_dev_of, msb_host_of;
+  bool ms_cluster = false;
+  uint32_t ms_cm_depth = 0;  // deepest level of Cuthill-McKee's own BFS (order_nodes)
+  uint32_t wms_bw = 1;       // bandwidth of the Cuthill-McKee ids over live records (kWms's skip)
+  uint32_t* d_msb_dev_of = nullptr;
+  uint32_t* d_msb_host_of = nullptr;
   // multi-source Bellman-Ford (kWms): in-link slots per Cuthill-McKee node,
   // rebuilt with the multi-source layout; wms_ok: the graph qualifies (every
   // degree <= 8, metrics < 2^15, N < 20,481); wms_k slots per node (4 or 8)
@@ -199,6 +213,10 @@ void free_graph_device(orh_graph* g) {
   (void)hipFree(g->d_ms_recs);
   (void)hipFree(g->d_ms_dev_of);
   (void)hipFree(g->d_ms_host_of);
+  (void)hipFree(g->d_msb_dev_of);
+  (void)hipFree(g->d_msb_host_of);
+  g->d_msb_dev_of = nullptr;
+  g->d_msb_host_of = nullptr;
   (void)hipFree(g->d_name_rank);
   (void)hipFree(g->d_rev);
   g->d_rev = nullptr;
@@ -259,39 +277,14 @@ uint32_t choose_ell_k(const orh_graph* g) {
   return deg[deg.size() * 9 / 10] > 4 ? 8 : 4;
 }
 
-// Cuthill-McKee: BFS from a low-degree node of each component, neighbours
-// visited in ascending degree (then host id) order
+// The node orders of the multi-source layouts (host/ms_order.h): Cuthill-McKee
+// for all of them, the cluster order for the multi-source BFS of deep graphs
 void order_nodes(orh_graph* g) {
   const uint32_t N = g->n_nodes;
   auto& host_of = g->ms_host_of;
   auto& dev_of = g->ms_dev_of;
-  host_of.clear();
-  host_of.reserve(N);
-  dev_of.assign(N, 0xFFFFFFFFu);
-  std::vector<uint32_t> deg(N), by_deg(N), nb;
-  for (uint32_t v = 0; v < N; ++v) {
-    deg[v] = g->dn_ptr[v + 1] - g->dn_ptr[v];
-    by_deg[v] = v;
-  }
-  std::stable_sort(by_deg.begin(), by_deg.end(),
-                   [&](uint32_t a, uint32_t b) { return deg[a] < deg[b]; });
-  for (uint32_t root : by_deg) {
-    if (dev_of[root] != 0xFFFFFFFFu) continue;
-    size_t head = host_of.size();
-    dev_of[root] = static_cast<uint32_t>(host_of.size());
-    host_of.push_back(root);
-    while (head < host_of.size()) {
-      const uint32_t v = host_of[head++];
-      nb.clear();
-      for (uint32_t k = g->dn_ptr[v]; k < g->dn_ptr[v + 1]; ++k)
-        if (dev_of[g->dn[k]] == 0xFFFFFFFFu) nb.push_back(g->dn[k]);
-      std::stable_sort(nb.begin(), nb.end(), [&](uint32_t a, uint32_t b) { return deg[a] < deg[b]; });
-      for (uint32_t u : nb) {
-        dev_of[u] = static_cast<uint32_t>(host_of.size());
-        host_of.push_back(u);
-      }
-    }
-  }
+  const uint32_t depth = orh::ms_cm_order(N, g->dn_ptr.data(), g->dn.data(), host_of, dev_of);
+  g->ms_cm_depth = depth;
   // ORH_MS_ORDER=host (A/B): the host order itself. Its slices are runs of
   // host ids, so the multi-source BFS writes the u32 distance rows straight
   // from its level assembly (no ms_finalize pass) and a wave's gathers read
@@ -305,6 +298,33 @@ void order_nodes(orh_graph* g) {
   g->ms_identity = fe && strcmp(fe, "host") == 0;
   if (g->ms_identity)
     for (uint32_t v = 0; v < N; ++v) dev_of[v] = host_of[v] = v;
+  // The multi-source BFS's order. Cuthill-McKee's 64-node slices are pieces of
+  // a BFS level (on the C2 grid: of an anti-diagonal, 126 hops end to end), so
+  // every slice stays short of some bit for ~100 levels and its arrivals come
+  // a few lanes at a time; the search pays per (slice, level), not per node.
+  // The cluster order makes the slices compact (ms_cluster_order;
+  // tools/ms_order_model.py: 0.40x the log store instructions and 0.64x the
+  // open slice-levels on C2). That only pays where arrivals spread over many
+  // levels: by default a graph takes it when Cuthill-McKee's own BFS is at
+  // least kMsClusterDepth levels deep (a Clos is 4-6 deep and keeps
+  // Cuthill-McKee; DESIGN.md section 5 has the measurements).
+  // ORH_MS_ORDER=cluster / cm force either
+  constexpr uint32_t kMsClusterDepth = 32;
+  g->ms_cluster = !g->ms_identity && N > 0 &&
+                  (fe && strcmp(fe, "cluster") == 0 ? true
+                   : fe && strcmp(fe, "cm") == 0    ? false
+                                                    : depth >= kMsClusterDepth);
+  g->msb_dev_of.clear();
+  g->msb_host_of.clear();
+  if (g->ms_cluster)
+    orh::ms_cluster_order(N, g->dn_ptr.data(), g->dn.data(), host_of.data(), dev_of.data(), g->msb_host_of,
+                          g->msb_dev_of);
+}
+
+// the id maps of the multi-source BFS layout (ms_recs, its batches, its kernels)
+const std::vector<uint32_t>& msb_dev_of(const orh_graph* g) { return g->ms_cluster ? g->msb_dev_of : g->ms_dev_of; }
+const std::vector<uint32_t>& msb_host_of(const orh_graph* g) {
+  return g->ms_cluster ? g->msb_host_of : g->ms_host_of;
 }
 
 uint2 device_record(const orh_graph* g, uint32_t v, uint32_t e, const uint32_t* dev_of = nullptr) {
@@ -345,20 +365,25 @@ void build_layout(orh_graph* g, std::vector<uint2>& recs, std::vector<uint32_t>&
   g->n_recs = static_cast<uint32_t>(recs.size());
 }
 
-// the ELL records again, rows and columns in Cuthill-McKee ids
+// the ELL records again, rows and columns in the multi-source BFS's ids
+// (cluster order, else Cuthill-McKee)
 void build_ms_layout(orh_graph* g, std::vector<uint2>& recs) {
   const uint32_t K = g->ell_k, N = g->n_nodes;
+  const std::vector<uint32_t>& dev_of = msb_dev_of(g);
+  const std::vector<uint32_t>& host_of = msb_host_of(g);
   recs.assign(g->n_recs, make_uint2(ORH_REC_SKIP, 1));
-  uint32_t ovf = N * K, bw = 0;
+  uint32_t ovf = N * K, bw = 0, bw_cm = 0;
   auto put = [&](uint32_t q, uint32_t dv, uint32_t v, uint32_t e) {
-    recs[q] = device_record(g, v, e, g->ms_dev_of.data());
+    recs[q] = device_record(g, v, e, dev_of.data());
     if (!(recs[q].x & ORH_REC_SKIP)) {
       const uint32_t u = recs[q].x & ORH_REC_COL_MASK;
       bw = std::max(bw, u > dv ? u - dv : dv - u);
+      const uint32_t cu = g->ms_dev_of[g->col[e]], cv = g->ms_dev_of[v];
+      bw_cm = std::max(bw_cm, cu > cv ? cu - cv : cv - cu);
     }
   };
   for (uint32_t dv = 0; dv < N; ++dv) {
-    const uint32_t v = g->ms_host_of[dv];
+    const uint32_t v = host_of[dv];
     const uint32_t e0 = g->row_ptr[v], d = g->row_ptr[v + 1] - e0, base = dv * K;
     const uint32_t inl = d <= K ? d : K - 1;
     for (uint32_t j = 0; j < inl; ++j) put(base + j, dv, v, e0 + j);
@@ -372,6 +397,9 @@ void build_ms_layout(orh_graph* g, std::vector<uint2>& recs) {
   // anti-diagonal, left") across a wave's consecutive Cuthill-McKee nodes,
   // consecutive frontier words instead of a mix of directions at the border
   // rows (bank conflicts of the ds_read_b32 gathers). ORH_MS_SORT=0: CSR order.
+  // (In cluster order, sorting by the neighbour's id minus the owner's - so
+  // that a cluster's border lanes keep each direction in one slot - measured
+  // the same: 19.54 against 19.56 ms per step, profiles/ms_cluster/step_ab.txt.)
   const char* es = getenv("ORH_MS_SORT");
   if (!(es && atoi(es) == 0)) {
     for (uint32_t dv = 0; dv < N; ++dv) {
@@ -393,6 +421,7 @@ void build_ms_layout(orh_graph* g, std::vector<uint2>& recs) {
   const bool on = e && atoi(e) == 1;
   g->ms_bw = on ? std::max(bw, 1u) : 0u;
   g->ms_bw_layout = std::max(bw, 1u);
+  g->wms_bw = std::max(bw_cm, 1u);
 }
 
 int sync_ms_layout(orh_graph* g) {
@@ -404,8 +433,16 @@ int sync_ms_layout(orh_graph* g) {
     const size_t nn = std::max<uint32_t>(g->n_nodes, 1);
     if (hipMalloc(&g->d_ms_recs, recs.size() * sizeof(uint2)) != hipSuccess ||
         hipMalloc(&g->d_ms_dev_of, nn * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&g->d_ms_host_of, nn * sizeof(uint32_t)) != hipSuccess)
+        hipMalloc(&g->d_ms_host_of, nn * sizeof(uint32_t)) != hipSuccess ||
+        (g->ms_cluster && (hipMalloc(&g->d_msb_dev_of, nn * sizeof(uint32_t)) != hipSuccess ||
+                           hipMalloc(&g->d_msb_host_of, nn * sizeof(uint32_t)) != hipSuccess)))
       return fail(ctx, ORH_E_NOMEM, "multi-source layout: device allocation failed");
+    if (g->ms_cluster) {
+      ORH_HIP(ctx, hipMemcpyAsync(g->d_msb_dev_of, g->msb_dev_of.data(), g->n_nodes * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, ctx->stream));
+      ORH_HIP(ctx, hipMemcpyAsync(g->d_msb_host_of, g->msb_host_of.data(), g->n_nodes * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, ctx->stream));
+    }
     ORH_HIP(ctx, hipMemcpyAsync(g->d_ms_dev_of, g->ms_dev_of.data(), g->n_nodes * sizeof(uint32_t),
                                 hipMemcpyHostToDevice, ctx->stream));
     ORH_HIP(ctx, hipMemcpyAsync(g->d_ms_host_of, g->ms_host_of.data(), g->n_nodes * sizeof(uint32_t),
@@ -1224,6 +1261,14 @@ int orh_graph_info(const orh_graph* g, uint32_t* n_nodes, uint32_t* n_edges) {
   if (!g) return ORH_E_INVALID;
   if (n_nodes) *n_nodes = g->n_nodes;
   if (n_edges) *n_edges = g->n_edges;
+  return ORH_OK;
+}
+
+int orh_graph_ms_order(const orh_graph* g, uint32_t* out, uint32_t cap, uint32_t* kind) {
+  if (!g || (cap && !out)) return ORH_E_INVALID;
+  const std::vector<uint32_t>& host_of = msb_host_of(g);
+  for (uint32_t i = 0; i < g->n_nodes && i < cap; ++i) out[i] = host_of[i];
+  if (kind) *kind = g->ms_cluster ? ORH_MS_ORDER_CLUSTER : g->ms_identity ? ORH_MS_ORDER_HOST : ORH_MS_ORDER_CM;
   return ORH_OK;
 }
 
@@ -2146,8 +2191,8 @@ int stage_request(orh_graph* g, const orh_spf_request* req, bool has_ign) {
   st.off_nbr_ptr = append(nbr_ptr);
   st.off_nbr_row = append(nbr_row);
   // multi-source batches (consecutive runs of ms_width rows): rows in
-  // ascending Cuthill-McKee id of their source, so a batch's sources are
-  // neighbours. (Measured alternatives on C2: BFS balls of 32 rows - 10.6
+  // ascending device id of their source (Cuthill-McKee here, the cluster
+  // order below), so a batch's sources are neighbours. (Measured alternatives on C2: BFS balls of 32 rows - 10.6
   // arrival levels per node and batch against 16.4 - swept in 0.92 ms
   // against 0.77; dispatching the batches middle-out changed nothing.)
   std::vector<uint32_t> order(st.n_rows);
@@ -2155,6 +2200,14 @@ int stage_request(orh_graph* g, const orh_spf_request* req, bool has_ign) {
   std::stable_sort(order.begin(), order.end(),
                    [&](uint32_t x, uint32_t y) { return g->ms_dev_of[srcs[x]] < g->ms_dev_of[srcs[y]]; });
   st.off_order = append(order);
+  // a graph in cluster order: the BFS batches in that order too (the
+  // Bellman-Ford plans keep the Cuthill-McKee batches above)
+  st.off_order_ms = st.off_order;
+  if (g->ms_cluster) {
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t x, uint32_t y) { return g->msb_dev_of[srcs[x]] < g->msb_dev_of[srcs[y]]; });
+    st.off_order_ms = append(order);
+  }
   drain_deferred(ctx);  // a deferred phase 2 may still read the staged request
   int rc = ensure_graph_req(g, staging.size());
   if (rc) return rc;
@@ -2438,15 +2491,15 @@ int fill_spf_args(orh_graph* g, const SweepFacts& f, const SweepPlan& sp, const 
     if (rc) return rc;
     a.ms_log = log_bytes ? reinterpret_cast<uint64_t*>(ctx->d_ms_lvl + halves * scratch) : nullptr;
     a.recs = g->d_ms_recs;
-    a.dev_of = g->d_ms_dev_of;
-    a.host_of = g->d_ms_host_of;
+    a.dev_of = g->ms_cluster ? g->d_msb_dev_of : g->d_ms_dev_of;
+    a.host_of = g->ms_cluster ? g->d_msb_host_of : g->d_ms_host_of;
     a.ms_lvl = ctx->d_ms_lvl + (*defer ? ctx->p2_half * scratch : 0);
     a.lvl_pitch = (N + 15u) & ~15u;
     rc = ensure_lvl_rows(ctx, static_cast<size_t>(sp.n_rows) * a.lvl_pitch);
     if (rc) return rc;
     a.lvl_rows = ctx->d_lvl_rows;
   }
-  a.order = g->d_req + st.off_order;
+  a.order = g->d_req + (sp.run.variant == V::kMsBfs ? st.off_order_ms : st.off_order);
   a.srcs = g->d_req + 1;
   a.ignore_ptr = f.has_ign ? g->d_req + st.off_ign_ptr : nullptr;
   a.ignore_links = f.has_ign ? g->d_req + st.off_ign : nullptr;
@@ -2483,7 +2536,7 @@ int fill_spf_args(orh_graph* g, const SweepFacts& f, const SweepPlan& sp, const 
     a.dev_of = g->d_ms_dev_of;
     a.wms_slots = g->d_wms;
     a.wms_limit = 0xFFFEu - g->wms_maxw;
-    a.ms_bw = k.wms_skip ? g->ms_bw_layout : 0u;
+    a.ms_bw = k.wms_skip ? g->wms_bw : 0u;
     a.recs_k = g->ell_k;
     a.wms_band = k.wms_band ? 1u : 0u;
   }
