@@ -202,6 +202,10 @@ typedef struct orh_spf_info {
                              kernel, this many per batch (the sweep could flag rows and the graph
                              has its wide layout); 0: redone per source (ORH_WMS_WIDE_REDO=0), no
                              row can be flagged, or another plan */
+  uint32_t ms_adj;        /* MS-BFS: adjacency skip on - a 64-node slice runs a level only if a
+                             slice holding a neighbour of its nodes, or itself, gained a bit the
+                             level before (by default in cluster order, except under the latency and
+                             lone-sweep plans; ORH_MS_ADJ=0 / 1), else 0 */
 } orh_spf_info;
 int orh_last_spf_info(const orh_ctx* ctx, orh_spf_info* out);
 /* device time (HIP events on the context stream) of the last orh_spf_run;

@@ -450,6 +450,7 @@ class SpfSweep {
     d["hop_dist"] = i.hop_dist;
     d["ms_threads"] = i.ms_threads;
     d["ms_skip"] = i.ms_skip;
+    d["ms_adj"] = i.ms_adj;
     d["ms_direct"] = i.ms_direct;
     d["wsl_links"] = i.wsl_links;
     d["wsl_slots"] = i.wsl_slots;
@@ -653,6 +654,33 @@ PYBIND11_MODULE(_openr_host, m) {
     const uint32_t depth = orh::ms_cm_order(n, ptr.data(), dn.data(), cmHost, cmDev);
     orh::ms_cluster_order(n, ptr.data(), dn.data(), cmHost.data(), cmDev.data(), clHost, clDev);
     return py::make_tuple(cmHost, depth, clHost);
+  });
+  // the slice adjacency of an order (ms_order.h; no device): for neighbour
+  // lists (every record a node has: repeats, down links and itself allowed)
+  // and an order as node per device id, per 64-id slice the ascending list of
+  // the slices holding a neighbour of its nodes, itself included; and the
+  // kernel's bitmask words of them (empty past its envelope)
+  m.def("ms_slice_adjacency", [](const std::vector<std::vector<uint32_t>>& adj, const std::vector<uint32_t>& hostOf) {
+    const uint32_t n = static_cast<uint32_t>(adj.size());
+    if (hostOf.size() != n) throw std::invalid_argument("ms_slice_adjacency: order length != node count");
+    std::vector<uint32_t> ptr(n + 1, 0), nb, devOf(n, orh::kMsOrderNone);
+    for (uint32_t d = 0; d < n; ++d) {
+      if (hostOf[d] >= n || devOf[hostOf[d]] != orh::kMsOrderNone)
+        throw std::invalid_argument("ms_slice_adjacency: order is not a permutation");
+      devOf[hostOf[d]] = d;
+    }
+    for (uint32_t v = 0; v < n; ++v) {
+      for (uint32_t u : adj[v]) {
+        if (u >= n) throw std::invalid_argument("ms_slice_adjacency: neighbour id out of range");
+        nb.push_back(u);
+      }
+      ptr[v + 1] = static_cast<uint32_t>(nb.size());
+    }
+    std::vector<uint32_t> adjPtr, adjList;
+    orh::ms_slice_adjacency(n, ptr.data(), nb.data(), devOf.data(), adjPtr, adjList);
+    std::vector<std::vector<uint32_t>> out(adjPtr.size() - 1);
+    for (size_t s = 0; s + 1 < adjPtr.size(); ++s) out[s].assign(adjList.begin() + adjPtr[s], adjList.begin() + adjPtr[s + 1]);
+    return py::make_tuple(out, orh::ms_adjacency_masks(adjPtr, adjList));
   });
 
   py::class_<LinkState>(m, "LinkState")

@@ -117,4 +117,54 @@ inline void ms_cluster_order(uint32_t n, const uint32_t* dn_ptr, const uint32_t*
   }
 }
 
+// Slice adjacency of an order: for each 64-id slice (ids [64 s, 64 s + 64):
+// one wave's nodes of one j in spf_msbfs_kernel) the slices that hold a
+// neighbour of any of its nodes, the slice itself included, ascending. A node
+// can gain a frontier bit only from a neighbour, so a slice can gain one at
+// level L only if one of these slices gained one at level L - 1: the key of
+// the kernel's adjacency skip. Cluster order keeps the sets small (5.6 slices
+// on the 100 x 100 grid, 9 at most) where the id bandwidth is most of N.
+//
+// nb_ptr / nb: per node, every neighbour the layout can ever read - all CSR
+// records of the node, continuation ones and down or drained ones included,
+// repeats allowed - so the sets are a superset that up / down and metric
+// flips cannot invalidate; dev_of: node -> id. Fills adj_ptr [slices + 1]
+// and adj.
+inline void ms_slice_adjacency(uint32_t n, const uint32_t* nb_ptr, const uint32_t* nb, const uint32_t* dev_of,
+                               std::vector<uint32_t>& adj_ptr, std::vector<uint32_t>& adj) {
+  constexpr uint32_t kRun = 64;
+  const uint32_t slices = (n + kRun - 1) / kRun;
+  std::vector<std::vector<uint32_t>> sets(slices);
+  for (uint32_t s = 0; s < slices; ++s) sets[s].push_back(s);
+  for (uint32_t v = 0; v < n; ++v) {
+    std::vector<uint32_t>& set = sets[dev_of[v] / kRun];
+    for (uint32_t k = nb_ptr[v]; k < nb_ptr[v + 1]; ++k) set.push_back(dev_of[nb[k]] / kRun);
+  }
+  adj_ptr.assign(slices + 1, 0);
+  adj.clear();
+  for (uint32_t s = 0; s < slices; ++s) {
+    std::sort(sets[s].begin(), sets[s].end());
+    sets[s].erase(std::unique(sets[s].begin(), sets[s].end()), sets[s].end());
+    adj.insert(adj.end(), sets[s].begin(), sets[s].end());
+    adj_ptr[s + 1] = static_cast<uint32_t>(adj.size());
+  }
+}
+
+// The form spf_msbfs_kernel reads: per slice a bitmask over the slices,
+// kMsAdjWords words (bit t of word k: slice 32 k + t is adjacent), so the
+// kernel's envelope is kMsAdjSlices slices (16,384 nodes: every u32- and
+// u64-mask shape). Empty when the graph has more slices.
+constexpr uint32_t kMsAdjWords = 8;
+constexpr uint32_t kMsAdjSlices = 32 * kMsAdjWords;
+inline std::vector<uint32_t> ms_adjacency_masks(const std::vector<uint32_t>& adj_ptr,
+                                                const std::vector<uint32_t>& adj) {
+  const size_t slices = adj_ptr.empty() ? 0 : adj_ptr.size() - 1;
+  std::vector<uint32_t> words;
+  if (slices == 0 || slices > kMsAdjSlices) return words;
+  words.assign(slices * kMsAdjWords, 0u);
+  for (size_t s = 0; s < slices; ++s)
+    for (uint32_t k = adj_ptr[s]; k < adj_ptr[s + 1]; ++k) words[s * kMsAdjWords + adj[k] / 32] |= 1u << (adj[k] % 32);
+  return words;
+}
+
 }  // namespace orh

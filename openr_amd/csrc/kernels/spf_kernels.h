@@ -33,6 +33,8 @@ struct SpfArgs {
   uint32_t ms_pitch;          // multi-source BFS: frontier-array entries (> N)
   uint32_t ms_zero;           // multi-source BFS: index of the always-zero entry
   uint32_t ms_bw;             // multi-source BFS: layout bandwidth for the interval skip (0: no skip)
+  const uint32_t* ms_adj;     // multi-source BFS: slice adjacency bitmasks [slices][kMsAdjWords] for the
+                              // adjacency skip (null: off; never with ms_bw)
   uint32_t ms_width;          // multi-source BFS: sources per batch (<= mask bits)
   uint32_t ms_direct;         // multi-source BFS (u16 / u32 masks, host-order layout): the
                               // level assembly writes the rows itself (no ms_lvl, no finalize)
@@ -238,6 +240,8 @@ struct SpfPlan {
   uint32_t ms_j;        // multi-source BFS: nodes owned per thread (template)
   uint32_t ms_pitch;    // multi-source BFS: frontier-array entries
   uint32_t ms_skip;     // multi-source BFS: interval skip (latency plan)
+  uint32_t ms_own_cu;   // multi-source BFS: the latency or the lone-sweep plan - the batches have their
+                        // CUs to themselves, where the adjacency skip measured slower (ms_set_width)
   size_t pend_off;
   size_t lds_bytes;
 };

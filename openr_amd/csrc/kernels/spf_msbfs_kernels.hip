@@ -40,7 +40,7 @@ namespace orh {
 // >= 254 are written to the output row directly (marker 254), so any depth is
 // exact; 255 = unreached.
 //
-// Interval skip (kSkip): every live record v -> u has |u - v| <= bw, the
+// Interval skip (kMsSkipInterval): every live record v -> u has |u - v| <= bw, the
 // bandwidth of the layout's order (small in Cuthill-McKee order, which is
 // where the skip can pay; most of N in cluster order). If the nodes
 // that gained a bit at level L-1 span the ids [lo, hi], only nodes in
@@ -49,9 +49,34 @@ namespace orh {
 // frontier entries. The interval is two LDS words per level (wave min / max
 // reductions); the per-slice test is scalar, so the variant costs no VGPRs
 // beyond the two running bounds (a slice-bitmap form of the same skip needed
-// 117 VGPRs, one workgroup per CU, and ran 1.4x slower). A skipped node keeps
-// a stale f_nxt entry from two levels back: its bits reached every neighbour
-// by the previous level, so it only repeats visited bits (see below).
+// 117 VGPRs, one workgroup per CU, and ran 1.4x slower).
+//
+// Adjacency skip (kMsSkipAdj, a.ms_adj): cluster order makes the id bandwidth
+// most of N but keeps the slices a slice touches few (ms_slice_adjacency,
+// host/ms_order.h: 6.6 on the 10k grid), so the key is which slices gained a
+// bit, not an id interval. s_act holds one bit per slice in three phases,
+// like s_lo / s_hin: during level L a wave whose slice has any arrival
+// (nx != 0 before the overloaded-node mask: conservative) ORs the slice's bit
+// into phase L % 3 and phase (L + 1) % 3 is cleared; the sources' slices are
+// marked where the sources are planted. Right after level L - 1's barrier,
+// with the progress flag (one LDS round trip), lane 8 q + k reads word k of
+// phase (L - 1) % 3; at the top of level L it ANDs it with word k of the
+// adjacency mask of the wave's slice 8 r + q, which it keeps in adjm[r], and
+// one ballot per r gives the wave-uniform todo bits: slice j is todo iff a
+// slice adjacent to it, or itself, was marked. A group runs only if it is open and one of its slices
+// is todo, so it keeps the group of 2 and its back-to-back gathers. The
+// adjacency is built from every record a node has, down ones included, so
+// link flips cannot invalidate it. Measured: the 2-lane C2 step 19.41 ->
+// 18.83 ms; slower where a batch has its CU to itself, so the latency and
+// lone-sweep plans leave it off (ms_set_width; profiles/ms_adj/).
+//
+// Why a skipped slice is harmless under either skip: it keeps stale f_nxt
+// entries, but a stale entry's bits reached every neighbour one level after
+// they were new - that neighbour's slice ran on that level, because the
+// node's own slice had just gained them (it was within reach / marked) - so
+// a stale entry only repeats bits its readers have visited (see below). And a
+// slice none of whose adjacent slices was marked reads stale or zero entries
+// alone: nothing can arrive.
 //
 // The search is latency-bound, not LDS-bound: on the 10k grid one workgroup
 // takes ~0.7 ms whether 32 or 313 of them run (two fit per CU), ~165 levels
@@ -86,7 +111,10 @@ __device__ inline uint32_t ms_col(const uint2& r, uint32_t zero) {
   return (r.x & (ORH_REC_SKIP | ORH_REC_CONT)) ? zero : (r.x & ORH_REC_COL_MASK);
 }
 
-template <int K, class M, int J, bool kSkip>
+constexpr int kMsSkipNone = 0, kMsSkipInterval = 1, kMsSkipAdj = 2;
+constexpr uint32_t kMsAdjWords = 8;  // host/ms_order.h: words of a slice's adjacency mask
+
+template <int K, class M, int J, int kMode>
 __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   constexpr uint32_t kS = MsMask<M>::kS;
@@ -100,6 +128,8 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
   const V full = S >= 8 * sizeof(V) ? ~V(0) : (V(1) << S) - V(1);
   __shared__ uint32_t s_prog[3];
   __shared__ uint32_t s_lo[3], s_hin[3];  // per level: min / ~max id with a new frontier bit
+  constexpr bool kSkip = kMode == kMsSkipInterval, kAdj = kMode == kMsSkipAdj;
+  __shared__ uint32_t s_act[kAdj ? 3 : 1][kMsAdjWords];  // per level: the slices with an arrival, a bit each
   M* f_cur = reinterpret_cast<M*>(lds);
   M* f_nxt = f_cur + a.ms_pitch;
   // the ELL columns hold byte offsets into a frontier array (16 bits each:
@@ -123,9 +153,9 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
   uint64_t* wlog = kLog ? a.ms_log + (static_cast<size_t>(blockIdx.x) * waves + wave) * J * 64u * kS : nullptr;
   uint32_t wcnt = 0;  // events in this wave's log (wave-uniform)
   __shared__ uint32_t s_wcnt[16];
-  auto log_events = [&](int j, V nx, uint32_t lv) {
+  auto log_events = [&](int j, V nx, uint32_t lv) -> bool {  // true: the slice has an arrival
     const uint64_t m = __builtin_amdgcn_ballot_w64(nx != 0u);
-    if (!m) return;
+    if (!m) return false;
     if (nx) {
       const uint32_t pos = wcnt + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
                                                             __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
@@ -133,6 +163,7 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
                   min(lv, kLvlDirect);
     }
     wcnt += static_cast<uint32_t>(__builtin_popcountll(m));
+    return true;
   };
 #ifdef ORH_DIAG_STAMPS
   const uint64_t t_entry = __builtin_amdgcn_s_memtime();
@@ -144,6 +175,7 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
     s_lo[tid] = ~0u;
     s_hin[tid] = ~0u;
   }
+  if (kAdj && tid < 3 * kMsAdjWords) (&s_act[0][0])[tid] = 0u;
   if (!kLog) {  // every level byte starts as "unreached"
     uint4* l4 = reinterpret_cast<uint4*>(lvl);
     for (uint32_t i = tid; i < N * kS / 16; i += B) l4[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
@@ -159,6 +191,26 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
     const uint32_t src = a.dev_of[a.srcs[a.order[b0 + tid]]];
     atomicMin(&s_lo[0], src);
     atomicMin(&s_hin[0], ~src);
+  }
+  if (kAdj && tid < S) {  // level 0's marks: the sources' slices, wherever they are
+    const uint32_t sl = a.dev_of[a.srcs[a.order[b0 + tid]]] >> 6;
+    atomicOr(&s_act[0][sl >> 5], 1u << (sl & 31u));
+  }
+  // adjacency masks of this wave's slices: lane 8 q + k holds word k of
+  // slice j = 8 r + q (id slice j * waves + wave) in adjm[r]
+  constexpr int kAdjR = kAdj ? (J + 7) / 8 : 1;
+  uint32_t adjm[kAdjR];
+  if constexpr (kAdj) {
+    const uint32_t n_slices = (N + 63u) >> 6;
+#pragma unroll
+    for (int r = 0; r < kAdjR; ++r) {
+      const uint32_t j = 8u * r + (lane >> 3), sl = j * waves + wave;
+      adjm[r] = j < static_cast<uint32_t>(J) && sl < n_slices ? a.ms_adj[sl * kMsAdjWords + (lane & 7u)] : 0u;
+      // the load lands here, not in the level loop: a use the compiler cannot
+      // see through, or it waits for vmcnt(0) - and with it for every log
+      // store of the level before - at the top of each level
+      asm volatile("" : "+v"(adjm[r]));
+    }
   }
 
   uint32_t col[J][KH];
@@ -203,6 +255,11 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
 #endif
   const uint32_t bw = a.ms_bw;
   const uint32_t wave_base = __builtin_amdgcn_readfirstlane(tid & ~63u);
+  // adjacency skip: word lane & 7 of the previous level's marks, read right
+  // after the level barrier together with the progress flag (one LDS round
+  // trip a level, not two)
+  uint32_t act = 0u;
+  if constexpr (kAdj) act = s_act[0][lane & 7u];
   for (uint32_t level = 1;; ++level) {
     int prog = 0;
     // opaque per level: keeps the compiler from hoisting J * K unpacked LDS
@@ -217,6 +274,16 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
     // level so the 16 slice bases are not hoisted into SGPRs that spill)
     uint32_t slice = wave_base;
     if constexpr (kSkip) asm volatile("" : "+s"(slice));
+    // adjacency skip: bit 8 q.. of todo[r] set iff slice 8 r + q can gain a bit
+    uint64_t todo[kAdjR];
+    if constexpr (kAdj) {
+#pragma unroll
+      for (int r = 0; r < kAdjR; ++r) {
+        asm volatile("" : "+v"(adjm[r]));
+        todo[r] = __builtin_amdgcn_ballot_w64((act & adjm[r]) != 0u);
+      }
+      if (tid < kMsAdjWords) s_act[(level + 1u) % 3u][tid] = 0u;  // read at level - 1, written at level + 1
+    }
     if constexpr (kSkip) {
       const uint32_t lo = __builtin_amdgcn_readfirstlane(s_lo[(level + 2u) % 3u]);
       const uint32_t hi = ~__builtin_amdgcn_readfirstlane(s_hin[(level + 2u) % 3u]);
@@ -241,6 +308,10 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
     for (int j0 = 0; j0 < J; j0 += G) {
       const uint32_t sl = slice;
       if constexpr (kSkip) slice += B;
+      if constexpr (kAdj) {  // j0 and G are even: the group's slices sit in one todo word
+        static_assert(G == 2, "the adjacency skip tests groups of 2 slices");
+        if (!((todo[j0 / 8] >> (8 * (j0 % 8))) & 0xFFFFull)) continue;
+      }
       bool open = false;
 #pragma unroll
       for (int g = 0; g < G; ++g) open |= vis[j0 + g] != full;
@@ -283,9 +354,12 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
 #ifdef ORH_DIAG_STAMPS
         const uint64_t t_s0 = __builtin_amdgcn_s_memtime();
 #endif
+        bool any = false;  // wave-uniform: the slice has an arrival
 #ifndef ORH_EXP_NO_LVL_STORE  // timing experiment only: drops the level bytes
-        if (kLog) log_events(j, nx, level);
+        if (kLog) any = log_events(j, nx, level);
 #endif
+        if (kAdj && !kLog) any = __builtin_amdgcn_ballot_w64(nx != 0u) != 0u;
+        if constexpr (kAdj) jm |= (any ? 1u : 0u) << j;
         if (nx) {
           prog = 1;
 #ifndef ORH_EXP_NO_LVL_STORE
@@ -318,6 +392,13 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
         if constexpr (kSkip) jm |= (__builtin_amdgcn_ballot_w64(nx != 0u) != 0u ? 1u : 0u) << j;
       }
     }
+    if constexpr (kAdj) {  // this wave's slices with an arrival into the level's marks: lane j, slice j
+      const uint32_t ln = me & 63u;
+      if (ln < static_cast<uint32_t>(J) && ((jm >> ln) & 1u)) {
+        const uint32_t sl = ln * (B >> 6) + (me >> 6);
+        atomicOr(&s_act[level % 3u][sl >> 5], 1u << (sl & 31u));
+      }
+    }
     if constexpr (kSkip) {  // this wave's new-frontier slices into the level's interval
       if (jm && (tid & 63u) == 0) {
         const uint32_t jl = static_cast<uint32_t>(__builtin_ctz(jm));
@@ -339,7 +420,9 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
     t_bar += __builtin_amdgcn_s_memtime() - t_b0;
     ++n_levels;
 #endif
-    if (!s_prog[level % 3u]) break;
+    const uint32_t progressed = s_prog[level % 3u];
+    if constexpr (kAdj) act = s_act[level % 3u][me & 7u];
+    if (!progressed) break;
     if (tid == 0) s_prog[(level + 2u) % 3u] = 0u;  // the previous level's flag, read before this barrier
     M* t = f_cur;
     f_cur = f_nxt;
@@ -518,8 +601,10 @@ static hipError_t launch_ms_j(const SpfPlan& plan, const SpfArgs& a, uint32_t n_
   }
   const SpfArgs& b = a;
   if (a.ms_bw)
-    return launch(spf_msbfs_kernel<K, M, J, true>, b, batches, plan.block, lds, s);
-  return launch(spf_msbfs_kernel<K, M, J, false>, b, batches, plan.block, lds, s);
+    return launch(spf_msbfs_kernel<K, M, J, kMsSkipInterval>, b, batches, plan.block, lds, s);
+  if (a.ms_adj)
+    return launch(spf_msbfs_kernel<K, M, J, kMsSkipAdj>, b, batches, plan.block, lds, s);
+  return launch(spf_msbfs_kernel<K, M, J, kMsSkipNone>, b, batches, plan.block, lds, s);
 }
 
 template <int K, class M>
@@ -583,6 +668,7 @@ void ms_set_width(SpfPlan& plan, uint32_t n_nodes, uint32_t n_rows, uint32_t n_c
   // 1,254 sources measured 0.785 vs 0.748 ms with it, profiles/r04/
   // f_strong_rehearsal_skip.txt vs e_strong_rehearsal.txt)
   plan.ms_skip = 0;
+  plan.ms_own_cu = 0;
   const LaunchKnobs knobs = launch_knobs();
   {
     const bool plans = knobs.ms_latency != 0 && !knobs.ms_block_set;
@@ -592,14 +678,25 @@ void ms_set_width(SpfPlan& plan, uint32_t n_nodes, uint32_t n_rows, uint32_t n_c
       plan.block = 1024;
       plan.ms_j = (j + 3) & ~3u;
       plan.ms_skip = knobs.ms_latency == 2;
+      // a batch alone on its CU is bound by the per-level latency chain, which
+      // the adjacency skip lengthens (its marks are read after the barrier)
+      // and skipped gathers do not shorten: the C5 area graph swept in 0.122
+      // against 0.111 ms with it, the 70 x 70 grid in 0.227 against 0.215
+      // (profiles/ms_adj/order_ab.txt), so this plan leaves it off
+      plan.ms_own_cu = 1;
     } else if (plans && alone && plan.block == 512) {
       // lone-sweep plan: no other sweep in flight on the device, so the
       // batches do not share CUs with other streams' kernels and 12 waves
       // per batch cut the per-level time (one C2 sweep 0.82 -> 0.68 ms of
       // MS-BFS); under concurrent sweeps 8 waves stay (the 4-lane step
-      // 24.8 vs 26.3 ms at 12, profiles/r04/ai_ms_block_ab.txt)
+      // 24.8 vs 26.3 ms at 12, profiles/r04/ai_ms_block_ab.txt). The plan
+      // needs two 12-wave batches on a CU, 6 waves per SIMD, 80 VGPRs: the
+      // adjacency variant's J = 16 takes 81, one batch per CU, and the lone
+      // C2 sweep ran 1.08 against 0.95 ms with it (profiles/ms_adj/
+      // lone_ab.txt), so this plan leaves the adjacency skip off too
       const uint32_t j12 = (n_nodes + 767) / 768;
       if (j12 <= 32) {
+        plan.ms_own_cu = 1;
         plan.block = 768;
         plan.ms_j = (j12 + 3) & ~3u;
       }

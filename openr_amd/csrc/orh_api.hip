@@ -154,6 +154,13 @@ struct orh_graph {
   uint32_t wms_bw = 1;       // bandwidth of the Cuthill-McKee ids over live records (kWms's skip)
   uint32_t* d_msb_dev_of = nullptr;
   uint32_t* d_msb_host_of = nullptr;
+  // slice adjacency of the multi-source BFS layout (ms_slice_adjacency,
+  // host/ms_order.h) as the kernel's bitmasks [slices][kMsAdjWords], rebuilt
+  // with the layout; empty past kMsAdjSlices slices. ms_adj_on: the sweeps
+  // take the adjacency skip (cluster order by default, ORH_MS_ADJ)
+  std::vector<uint32_t> ms_adj_words;
+  bool ms_adj_on = false, ms_adj_forced = false;
+  uint32_t* d_ms_adj = nullptr;
   // multi-source Bellman-Ford (kWms): in-link slots per Cuthill-McKee node,
   // rebuilt with the multi-source layout; wms_ok: the graph qualifies (every
   // degree <= 8, metrics < 2^15, N < 20,481); wms_k slots per node (4 or 8)
@@ -217,6 +224,8 @@ void free_graph_device(orh_graph* g) {
   (void)hipFree(g->d_msb_host_of);
   g->d_msb_dev_of = nullptr;
   g->d_msb_host_of = nullptr;
+  (void)hipFree(g->d_ms_adj);
+  g->d_ms_adj = nullptr;
   (void)hipFree(g->d_name_rank);
   (void)hipFree(g->d_rev);
   g->d_rev = nullptr;
@@ -422,6 +431,19 @@ void build_ms_layout(orh_graph* g, std::vector<uint2>& recs) {
   g->ms_bw = on ? std::max(bw, 1u) : 0u;
   g->ms_bw_layout = std::max(bw, 1u);
   g->wms_bw = std::max(bw_cm, 1u);
+  // adjacency skip (spf_msbfs_kernel's kMsSkipAdj): the slices a slice can
+  // receive from, over every CSR entry of its nodes - down and drained ones
+  // too, and a free slot (its col is the node itself) - so only a change of
+  // the rows' neighbours, which rebuilds this layout, can change it. On where
+  // the cluster order is (it is what makes the sets small) and the slices fit
+  // the kernel's bitmasks; ORH_MS_ADJ=0: off, ORH_MS_ADJ=1: under any order
+  std::vector<uint32_t> adj_ptr, adj;
+  orh::ms_slice_adjacency(N, g->row_ptr.data(), g->col.data(), dev_of.data(), adj_ptr, adj);
+  g->ms_adj_words = orh::ms_adjacency_masks(adj_ptr, adj);
+  const char* ea = getenv("ORH_MS_ADJ");
+  const bool adj_on = ea && atoi(ea) == 0 ? false : ea && atoi(ea) == 1 ? true : g->ms_cluster;
+  g->ms_adj_on = adj_on && !g->ms_adj_words.empty();
+  g->ms_adj_forced = g->ms_adj_on && ea && atoi(ea) == 1;
 }
 
 int sync_ms_layout(orh_graph* g) {
@@ -435,7 +457,9 @@ int sync_ms_layout(orh_graph* g) {
         hipMalloc(&g->d_ms_dev_of, nn * sizeof(uint32_t)) != hipSuccess ||
         hipMalloc(&g->d_ms_host_of, nn * sizeof(uint32_t)) != hipSuccess ||
         (g->ms_cluster && (hipMalloc(&g->d_msb_dev_of, nn * sizeof(uint32_t)) != hipSuccess ||
-                           hipMalloc(&g->d_msb_host_of, nn * sizeof(uint32_t)) != hipSuccess)))
+                           hipMalloc(&g->d_msb_host_of, nn * sizeof(uint32_t)) != hipSuccess)) ||
+        (!g->ms_adj_words.empty() &&
+         hipMalloc(&g->d_ms_adj, g->ms_adj_words.size() * sizeof(uint32_t)) != hipSuccess))
       return fail(ctx, ORH_E_NOMEM, "multi-source layout: device allocation failed");
     if (g->ms_cluster) {
       ORH_HIP(ctx, hipMemcpyAsync(g->d_msb_dev_of, g->msb_dev_of.data(), g->n_nodes * sizeof(uint32_t),
@@ -450,6 +474,9 @@ int sync_ms_layout(orh_graph* g) {
   }
   ORH_HIP(ctx, hipMemcpyAsync(g->d_ms_recs, recs.data(), recs.size() * sizeof(uint2),
                               hipMemcpyHostToDevice, ctx->stream));
+  if (g->d_ms_adj)  // the slice count is the graph's: the size never changes
+    ORH_HIP(ctx, hipMemcpyAsync(g->d_ms_adj, g->ms_adj_words.data(), g->ms_adj_words.size() * sizeof(uint32_t),
+                                hipMemcpyHostToDevice, ctx->stream));
   ORH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // recs is a local
   g->ms_dirty = false;
   return ORH_OK;
@@ -2478,6 +2505,10 @@ int fill_spf_args(orh_graph* g, const SweepFacts& f, const SweepPlan& sp, const 
     // the interval skip: opt-in for every sweep (ORH_MS_SKIP=1) or for the
     // latency plan alone (ORH_MS_LATENCY=2)
     a.ms_bw = g->ms_bw ? g->ms_bw : sp.run.ms_skip ? g->ms_bw_layout : 0u;
+    // the adjacency skip, unless the interval skip is on (the two never run
+    // together) or the plan is the latency or the lone-sweep one, where it
+    // measured slower (ms_set_width); ORH_MS_ADJ=1 takes it even there
+    a.ms_adj = !a.ms_bw && g->ms_adj_on && (!sp.run.ms_own_cu || g->ms_adj_forced) ? g->d_ms_adj : nullptr;
     a.ms_width = sp.run.ms_width;
     // host-order layout, u16 / u32 masks: the rows come out of the search
     // kernel itself
@@ -2677,6 +2708,7 @@ orh_spf_info search_info(const orh_graph* g, const SweepPlan& sp, const orh::Spf
   info.batch_sources = ms ? sp.run.ms_width : 0;
   info.ms_threads = ms ? sp.run.block : 0;
   info.ms_skip = ms && a.ms_bw ? 1u : 0u;
+  info.ms_adj = ms && a.ms_adj ? 1u : 0u;
   info.ms_direct = ms ? a.ms_direct : (sp.wms || sp.wsl || sp.wide) && g->ms_identity ? 1u : 0u;
   if (sp.wsl) {
     info.batch_sources = orh::wms_sources(g->n_nodes, g->ctx->lds_limit);

@@ -13,6 +13,23 @@ level and prints, summed over the batches:
   stores      (slice, level) pairs with an arrival - log store instructions
   open        (slice, level) pairs whose gathers run - slices not yet full
 
+and what the adjacency skip (kMsSkipAdj; slice_adjacency below restates
+ms_slice_adjacency of csrc/host/ms_order.h) leaves of that. A slice is todo
+at level L when a slice adjacent to it, or itself, had an arrival at level
+L - 1 (level 0: the sources' slices); no arrival ever falls outside the todo
+slices (asserted on every level):
+
+  need        open slices that are todo
+  open_g      groups of 2 slices of a wave (slices j * waves + w and
+              (j + 1) * waves + w, j even) with an open slice: what runs today
+  need_g      groups with an open slice and a todo slice: the kernel's exact
+              run condition
+  crit        groups run by the busiest wave, summed over the batch-levels
+              (what the level barrier waits for), without / with the skip,
+              and the same per level
+
+The workgroup is plan_spf's: 256 threads up to 4,096 nodes, 512 up to 16,384.
+
   tools/ms_order_model.py grid:100 cm cluster host
   tools/ms_order_model.py ring:2011:4 cluster
 
@@ -155,9 +172,55 @@ def cluster_order(adj, cm_host_of):
     return host_of
 
 
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def slice_adjacency(adj, host_of):
+    """ms_slice_adjacency (csrc/host/ms_order.h) restated: per 64-id slice of
+    the order, the ascending list of the slices that hold a neighbour of any
+    of its nodes, the slice itself included."""
+    n = len(adj)
+    dev_of = [0] * n
+    for d, v in enumerate(host_of):
+        dev_of[v] = d
+    sets = [{s} for s in range((n + RUN - 1) // RUN)]
+    for v, a in enumerate(adj):
+        sets[dev_of[v] // RUN].update(dev_of[u] // RUN for u in a)
+    return [sorted(x) for x in sets]
+
+
+def plan_waves(n):
+    """Waves per workgroup of plan_spf's multi-source BFS shape."""
+    return 4 if n <= 4096 else 8 if n <= 16384 else 12
+
+
 def model(adj, host_of):
     """Replays the all-sources sweep; returns (batches, levels, events, stores, open)."""
+    r = replay(adj, host_of)
+    return r["batches"], r["levels"], r["events"], r["stores"], r["open"]
+
+
+def replay(adj, host_of, sadj=None, waves=None):
+    """Replays the all-sources sweep with the adjacency skip's bookkeeping
+    (sadj: the slice adjacency, default slice_adjacency's; waves: per
+    workgroup, default plan_waves'). Returns the columns by name."""
     n = len(adj)
+    sadj = slice_adjacency(adj, host_of) if sadj is None else sadj
+    waves = plan_waves(n) if waves is None else waves
+    n_sl = (n + RUN - 1) // RUN
+    assert len(sadj) == n_sl
+    jn = 4 * _ceil(_ceil(n, RUN * waves), 4)  # nodes per thread (plan_spf)
+    amat = np.zeros((n_sl, n_sl), dtype=np.int32)
+    for t, lst in enumerate(sadj):
+        amat[t, lst] = 1
+
+    def grouped(x):  # per slice -> per (group, wave): any of the group's 2 slices
+        pad = np.zeros(jn * waves, dtype=bool)
+        pad[:n_sl] = x
+        return pad.reshape(jn // 2, 2, waves).any(axis=1)
+
+    need = open_g = need_g = crit_open = crit_need = arrive = 0
     dev_of = np.empty(n, dtype=np.int64)
     dev_of[np.asarray(host_of)] = np.arange(n)
     kmax = max(1, max(len(a) for a in adj))
@@ -175,22 +238,36 @@ def model(adj, host_of):
         f[:n] = vis
         arrived = vis != 0
         events += int(arrived.sum())
-        stores += int(np.add.reduceat(arrived, starts).astype(bool).sum())
+        marked = np.add.reduceat(arrived, starts).astype(bool)  # level 0: the sources' slices
+        stores += int(marked.sum())
         batches += 1
         while True:
             short = vis != full
-            opened += int(np.add.reduceat(short, starts).astype(bool).sum())
+            open_s = np.add.reduceat(short, starts).astype(bool)
+            opened += int(open_s.sum())
+            todo = amat @ marked.astype(np.int32) > 0
+            need += int((open_s & todo).sum())
+            og, tg = grouped(open_s), grouped(todo)
+            open_g += int(og.sum())
+            need_g += int((og & tg).sum())
+            crit_open += int(og.sum(axis=0).max())
+            crit_need += int((og & tg).sum(axis=0).max())
             nx = np.bitwise_or.reduce(f[nbr], axis=1) & ~vis
             arrived = nx != 0
             k = int(arrived.sum())
+            marked = np.add.reduceat(arrived, starts).astype(bool)
+            assert not (marked & ~todo).any(), "an arrival outside the todo slices"
             if not k:
                 break
             levels += 1
             vis |= nx
             events += k
-            stores += int(np.add.reduceat(arrived, starts).astype(bool).sum())
+            stores += int(marked.sum())
+            arrive += int(marked.sum())
             f[:n] = nx
-    return batches, levels, events, stores, opened
+    return {"batches": batches, "levels": levels, "events": events, "stores": stores, "open": opened,
+            "need": need, "arrive": arrive, "open_g": open_g, "need_g": need_g, "crit_open": crit_open,
+            "crit_need": crit_need, "waves": waves, "j": jn}
 
 
 def main(argv):
@@ -199,8 +276,10 @@ def main(argv):
     adj = topology(argv[1])
     n = len(adj)
     cm, depth = cm_order(adj)
-    print(f"{argv[1]}: {n} nodes, Cuthill-McKee BFS depth {depth}; 512 threads' slices of {RUN}, batches of {BATCH}")
-    print(f"{'order':8s} {'levels/batch':>12s} {'events':>12s} {'/node':>6s} {'stores':>10s} {'open':>10s}")
+    print(f"{argv[1]}: {n} nodes, Cuthill-McKee BFS depth {depth}; slices of {RUN}, batches of {BATCH}, "
+          f"{plan_waves(n)} waves a workgroup")
+    print(f"{'order':8s} {'levels/batch':>12s} {'events':>12s} {'/node':>6s} {'stores':>10s} {'open':>10s}"
+          f" {'need':>10s} {'open_g':>10s} {'need_g':>10s} {'crit':>17s} {'/level':>11s} {'adj/slice':>10s}")
     for name in argv[2:]:
         if name == "cm":
             order = cm
@@ -211,8 +290,15 @@ def main(argv):
         else:
             raise SystemExit(f"unknown order {name!r}")
         assert sorted(order) == list(range(n))
-        b, lv, ev, stc, op = model(adj, order)
-        print(f"{name:8s} {lv / b:12.1f} {ev:12d} {ev / (b * n):6.2f} {stc:10d} {op:10d}", flush=True)
+        sadj = slice_adjacency(adj, order)
+        r = replay(adj, order, sadj)
+        b, lv, ev, stc, op = r["batches"], r["levels"], r["events"], r["stores"], r["open"]
+        bl = lv + b  # batch-levels the loop runs: one more per batch, which finds nothing
+        crit = f"{r['crit_open']}/{r['crit_need']}"
+        per = f"{r['crit_open'] / bl:.1f}/{r['crit_need'] / bl:.1f}"
+        deg = f"{sum(map(len, sadj)) / len(sadj):.1f}/{max(map(len, sadj))}"
+        print(f"{name:8s} {lv / b:12.1f} {ev:12d} {ev / (b * n):6.2f} {stc:10d} {op:10d}"
+              f" {r['need']:10d} {r['open_g']:10d} {r['need_g']:10d} {crit:>17s} {per:>11s} {deg:>10s}", flush=True)
 
 
 if __name__ == "__main__":
