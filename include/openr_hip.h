@@ -405,7 +405,8 @@ int orh_ksp2_batch(orh_graph* g, uint32_t n_pairs, const uint32_t* h_src, const 
  * deletePrefix PrefixState.cpp:17-56). Prefix p is a dense id chosen by the
  * caller; its advertisements are an ordered list of orh_adv records (the
  * order only numbers them: route selection reports the best one by its
- * position). Node names and areas are caller-side ids. */
+ * position). Node names and areas are caller-side ids; a list holds each
+ * (name, area) once, as PrefixEntries is a map over them. */
 typedef struct orh_prefix_set orh_prefix_set;
 
 typedef struct orh_adv {
@@ -430,11 +431,16 @@ typedef struct orh_adv {
 
 int orh_prefix_create(orh_ctx* ctx, orh_prefix_set** out);
 int orh_prefix_destroy(orh_prefix_set* ps);
-/* full upload: prefix p owns advs[adv_ptr[p] .. adv_ptr[p+1]) */
+/* full upload: prefix p owns advs[adv_ptr[p] .. adv_ptr[p+1]); one prefix
+ * holds at most 65,535 advertisements (ORH_E_INVALID beyond, here and in
+ * orh_prefix_apply_delta) */
 int orh_prefix_load(orh_prefix_set* ps, uint32_t n_prefix, const uint32_t* h_adv_ptr,
                     const orh_adv* h_advs, const uint8_t* h_prefix_flags);
 /* incremental: prefix ids[i] gets advs[adv_ptr[i] .. adv_ptr[i+1]) (an empty
- * list withdraws it; ids beyond the current count grow the set) */
+ * list withdraws it; ids beyond the current count grow the set, and the ids
+ * in between start withdrawn). An id may occur more than once in h_ids: its
+ * last list wins, on the host mirror and on the device, and n_adv_live of
+ * orh_prefix_info counts that list alone. */
 int orh_prefix_apply_delta(orh_prefix_set* ps, uint32_t n, const uint32_t* h_ids,
                            const uint32_t* h_adv_ptr, const orh_adv* h_advs,
                            const uint8_t* h_prefix_flags);
@@ -456,9 +462,21 @@ int orh_prefix_info(const orh_prefix_set* ps, uint32_t* n_prefix, uint32_t* n_ad
  * status[p]: ORH_SEL_NONE (no route), ORH_SEL_ROUTE (metric[p] = shortest,
  * best[p] = position of bestNodeArea in p's list, mask[p] = per area the OR of
  * the argmin advertisers' first-hop masks, zero for areas above the minimum),
- * or ORH_SEL_HOST (a case the host path keeps: BGP metric vectors, SR_MPLS /
- * KSP2 forwarding, minNexthop, self-advertised, unknown area, > 255
- * advertisers). */
+ * or ORH_SEL_HOST (a case the host path keeps). In order:
+ *   no advertisement (withdrawn)                          NONE
+ *   more than 64 advertisements (the kernel's candidate
+ *   sets are 64-bit words; kMaxAdvDevice)                 HOST
+ *   no reachable advertiser, or a v4 prefix without
+ *   ORH_SELECT_V4                                         NONE
+ *   an advertisement of `me` or of an area that is not
+ *   present (both count as reachable), or a reachable
+ *   BGP advertisement (metric vectors)                    HOST
+ *   after selection and the drained filter: SR_MPLS or
+ *   KSP2 forwarding (every chosen entry asks for it),
+ *   or a chosen entry with minNexthop                     HOST
+ *   no first hop towards the nearest chosen advertiser    NONE
+ * For NONE and HOST, metric[p] = ORH_UNREACHABLE and every mask word of p is
+ * zero; best[p] is written (below the list's length) but means nothing. */
 #define ORH_SEL_NONE 0
 #define ORH_SEL_ROUTE 1
 #define ORH_SEL_HOST 2

@@ -3625,15 +3625,25 @@ int orh_prefix_apply_delta(orh_prefix_set* ps, uint32_t n, const uint32_t* ids,
   const size_t old_n = ps->hdr.size();
   if (max_id >= old_n) ps->hdr.resize(static_cast<size_t>(max_id) + 1, make_uint2(0u, 0u));
   const uint32_t base = static_cast<uint32_t>(ps->pool.size());
-  std::vector<uint2> vals(n);
+  bool ascending = true;
   for (uint32_t i = 0; i < n; ++i) {
     uint2& h = ps->hdr[ids[i]];
     ps->live -= h.y & 0xFFFFu;
     const uint32_t c = adv_ptr[i + 1] - adv_ptr[i];
     h = make_uint2(base + adv_ptr[i], c | (uint32_t(pflags[i]) << 16));
     ps->live += c;
-    vals[i] = h;
+    ascending &= i == 0 || ids[i - 1] < ids[i];
   }
+  // an id given more than once keeps its last list (the mirror above already
+  // does): the scatter writes each id once, so no two threads race on a header
+  std::vector<uint32_t> uniq(ids, ids + n);
+  if (!ascending) {
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  }
+  const uint32_t n_set = static_cast<uint32_t>(uniq.size());
+  std::vector<uint2> vals(n_set);
+  for (uint32_t i = 0; i < n_set; ++i) vals[i] = ps->hdr[uniq[i]];
   ps->pool.insert(ps->pool.end(), advs, advs + n_adv);
   // mostly garbage: rebuild the pool from the live runs and re-upload
   if (ps->pool.size() > 4096 && ps->pool.size() > 2 * static_cast<size_t>(ps->live)) {
@@ -3661,15 +3671,15 @@ int orh_prefix_apply_delta(orh_prefix_set* ps, uint32_t n, const uint32_t* ids,
     ORH_HIP(ctx, hipMemcpyAsync(ps->d_pool + base, advs, static_cast<size_t>(n_adv) * sizeof(orh_adv),
                                 hipMemcpyHostToDevice, ctx->stream));
   // staging: ids[n] (padded to 8 bytes) | headers[n]
-  const size_t id_words = (n + 1) & ~1u;
-  std::vector<uint32_t> st(id_words + 2 * static_cast<size_t>(n));
-  std::copy(ids, ids + n, st.begin());
-  std::memcpy(st.data() + id_words, vals.data(), n * sizeof(uint2));
+  const size_t id_words = (n_set + 1) & ~1u;
+  std::vector<uint32_t> st(id_words + 2 * static_cast<size_t>(n_set));
+  std::copy(uniq.begin(), uniq.end(), st.begin());
+  std::memcpy(st.data() + id_words, vals.data(), n_set * sizeof(uint2));
   rc = stage(ps, st.size());
   if (rc) return rc;
   ORH_HIP(ctx, hipMemcpyAsync(ps->d_stage, st.data(), st.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   ORH_HIP(ctx, orh::launch_scatter_hdr(ps->d_hdr, ps->d_stage,
-                                       reinterpret_cast<const uint2*>(ps->d_stage + id_words), n,
+                                       reinterpret_cast<const uint2*>(ps->d_stage + id_words), n_set,
                                        ctx->stream));
   ORH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // st is a local
   return ORH_OK;
