@@ -206,8 +206,19 @@ typedef struct orh_spf_info {
                              slice holding a neighbour of its nodes, or itself, gained a bit the
                              level before (by default in cluster order, except under the latency and
                              lone-sweep plans; ORH_MS_ADJ=0 / 1), else 0 */
+  uint32_t hop_lean;      /* MS-BFS: the lean first-hop kernel ran (one mask word, at most 8 distinct
+                             neighbours, no ignore sets, a large batch, N a multiple of 4;
+                             ORH_HOP_LEAN=0 turns it off); hop_nodes / hop_split are its geometry */
+  uint32_t hop_redo;      /* lean first-hop kernel: capacity of the list of sources it may leave to
+                             the generic kernel (rows that hold levels >= 254), else 0; how many
+                             it left stays on the device */
 } orh_spf_info;
 int orh_last_spf_info(const orh_ctx* ctx, orh_spf_info* out);
+/* the bytewise first-hop test of the level-row kernels, as the device runs it
+ * (host build of the same function, for tests): 0x01 in every byte k where
+ * byte k of nbr_word + 1 == byte k of own_word and that byte is reached (not
+ * 255); byte src_byte (0..3, else none) of own_word counts as unreached */
+uint32_t orh_lvl_tight_word(uint32_t nbr_word, uint32_t own_word, uint32_t src_byte);
 /* device time (HIP events on the context stream) of the last orh_spf_run;
  * waits for that launch to finish */
 int orh_last_spf_ms(orh_ctx* ctx, double* ms_out);

@@ -455,6 +455,8 @@ class SpfSweep {
     d["wsl_links"] = i.wsl_links;
     d["wsl_slots"] = i.wsl_slots;
     d["wide_redo"] = i.wide_redo;
+    d["hop_lean"] = i.hop_lean;
+    d["hop_redo"] = i.hop_redo;
     return d;
   }
   py::tuple fetch(size_t i) {
@@ -1571,6 +1573,15 @@ PYBIND11_MODULE(_openr_host, m) {
         return py::make_tuple(changed, unicastToWire(e));
       });
 
+  // the level-row first-hop kernels' bytewise test, word by word (orh_lvl_tight_word)
+  m.def("lvl_tight_words", [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> nbr,
+                              py::array_t<uint32_t, py::array::c_style | py::array::forcecast> own, uint32_t srcByte) {
+    if (nbr.size() != own.size()) throw std::invalid_argument("lvl_tight_words: sizes differ");
+    py::array_t<uint32_t> out(nbr.size());
+    for (py::ssize_t k = 0; k < nbr.size(); ++k)
+      out.mutable_data()[k] = orh_lvl_tight_word(nbr.data()[k], own.data()[k], srcByte);
+    return out;
+  }, py::arg("nbr_words"), py::arg("own_words"), py::arg("src_byte"));
   m.def("device_count", [] {
     int n = 0;
     orh_device_count(&n);

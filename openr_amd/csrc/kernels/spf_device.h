@@ -163,6 +163,38 @@ __device__ inline void load_recs(const SpfArgs& a, uint32_t v, uint2 (&rec)[K]) 
 // (levels >= 254), 255 = unreached
 constexpr uint32_t kLvlDirect = 254u, kLvlNone = 255u;
 
+// The first-hop test over level bytes, four nodes per word op: source s has
+// neighbour n as a tight first hop towards v iff L_n(v) + 1 == L_s(v) with v
+// reached from s. The callers keep kLvlDirect bytes away (the levels behind
+// them are in the u32 rows).
+// 0x80 in every byte of z that is zero
+__host__ __device__ inline uint32_t lvl_zero_bytes(uint32_t z) {
+  return ~(((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z | 0x7F7F7F7Fu);
+}
+// a source's own level word with byte src_byte (0..3, else none: the source
+// itself, which has no next hops) forced to "unreached"
+__host__ __device__ inline uint32_t lvl_own_forced(uint32_t ow, uint32_t src_byte) {
+  return src_byte < 4u ? ow | (0xFFu << (src_byte * 8u)) : ow;
+}
+// 0x80 in every byte of a level word that is reached (not kLvlNone)
+__host__ __device__ inline uint32_t lvl_reached(uint32_t w) { return ~lvl_zero_bytes(~w) & 0x80808080u; }
+// 0x01 in every byte where nw + 1 == ot and ot is reached (`reached` =
+// lvl_reached(ot); a kernel whose rows hold no kLvlDirect byte passes
+// kLvlAllReached, which folds away: only nw = 254 increments to 255). The increment is bytewise mod 256: the low seven bits
+// carry into bit 7, which is then flipped back by the byte's own bit 7, so no
+// carry leaves a byte; a neighbour's 255 wraps to 0, a level only the source
+// holds, which lvl_own_forced turned into 255
+constexpr uint32_t kLvlAllReached = 0x80808080u;
+__host__ __device__ inline uint32_t lvl_tight(uint32_t nw, uint32_t ot, uint32_t reached) {
+  const uint32_t inc = ((nw & 0x7F7F7F7Fu) + 0x01010101u) ^ (nw & 0x80808080u);
+  return (lvl_zero_bytes(inc ^ ot) & reached) >> 7;
+}
+// the whole test of one neighbour word against one own word
+__host__ __device__ inline uint32_t lvl_tight_word(uint32_t nw, uint32_t ow, uint32_t src_byte) {
+  const uint32_t ot = lvl_own_forced(ow, src_byte);
+  return lvl_tight(nw, ot, lvl_reached(ot));
+}
+
 // workgroup barrier that orders LDS only (s_waitcnt lgkmcnt(0) + s_barrier);
 // the "memory" clobber keeps the compiler from moving LDS accesses across it
 __device__ inline void lds_barrier() {

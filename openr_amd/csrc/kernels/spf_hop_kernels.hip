@@ -161,7 +161,9 @@ __device__ inline bool has_byte_fe(uint32_t x) {  // some byte == kLvlDirect
 
 // One workgroup per (source, tile phase): the source's tight first links are
 // gathered once, then the workgroup walks tiles phase, phase + split, ...
-template <uint32_t kLvlPer>
+// kList: the sources a.redo_list[0, *a.redo_count) instead of all (the ones
+// first_hop_lean_kernel left), any grid striding over them
+template <uint32_t kLvlPer, bool kList = false>
 __global__ __launch_bounds__(kBlock) void first_hop_lvl_kernel(HopArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ uint32_t s_cnt;
@@ -174,7 +176,11 @@ __global__ __launch_bounds__(kBlock) void first_hop_lvl_kernel(HopArgs a) {
   // 8 XCDs; ORH_HOP_WG_PER_CU) XCD x = b % 8 owns a contiguous logical range
   // its workgroups stride through
   uint32_t lb, lb_end, lb_step;
-  if (gridDim.x >= a.n_logical) {
+  if constexpr (kList) {
+    lb = blockIdx.x;
+    lb_end = *a.redo_count * split;
+    lb_step = gridDim.x;
+  } else if (gridDim.x >= a.n_logical) {
     lb = xcd_block(blockIdx.x, gridDim.x, a.xcd_group);
     lb_end = lb + 1;
     lb_step = 1;
@@ -188,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void first_hop_lvl_kernel(HopArgs a) {
     lb_step = gridDim.x / kXcd;
   }
   for (; lb < lb_end; lb += lb_step) {
-  const uint32_t i = lb / split, phase = lb % split;
+  const uint32_t i = kList ? a.redo_list[lb / split] : lb / split, phase = lb % split;
   const uint32_t src = a.srcs[i];
   const uint32_t nb = a.nbr_ptr[i + 1] - a.nbr_ptr[i];
   const uint4* ent = reinterpret_cast<const uint4*>(lds + ((2 * nb + 3) & ~3u));
@@ -306,12 +312,7 @@ __global__ __launch_bounds__(kBlock) void first_hop_lvl_kernel(HopArgs a) {
           // L_s(v), bytewise mod 256 (an unreached 255 wraps to 0, a level
           // only the source holds, forced to 255 in ot)
 #pragma unroll
-          for (uint32_t q = 0; q < kWords; ++q) {
-            const uint32_t inc = ((nw[q] & 0x7F7F7F7Fu) + 0x01010101u) ^ (nw[q] & 0x80808080u);
-            const uint32_t z = inc ^ ot[q];
-            const uint32_t eq = ~(((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z | 0x7F7F7F7Fu);  // 0x80 per zero byte
-            pk[q] |= (eq >> 7) * bit;
-          }
+          for (uint32_t q = 0; q < kWords; ++q) pk[q] |= lvl_tight(nw[q], ot[q], kLvlAllReached) * bit;  // !direct: no kLvlDirect byte
         } else if (!direct) {  // plain levels, a rank past 7
 #pragma unroll
           for (uint32_t k = 0; k < kLvlPer; ++k)
@@ -349,12 +350,183 @@ __global__ __launch_bounds__(kBlock) void first_hop_lvl_kernel(HopArgs a) {
   }
 }
 
+// The lean form of first_hop_lvl_kernel for what a large plain sweep is made
+// of (launch_first_hop checks it): one mask word, ranks below 8 (a node's
+// mask is one byte), no ignore sets, N a multiple of 4 with 16-byte aligned
+// output rows, and no kLvlDirect byte in the rows a source reads - a source
+// whose own row or a neighbour's row is flagged in a.row_deep goes to
+// a.redo_list and first_hop_lvl_kernel<.., true> redoes it. Same results.
+//
+// A tile is Q strips of 1,024 nodes; in strip q wave w covers the 256 nodes
+// from q * 1024 + w * 256, lane l the four from 4 l: every row access is one
+// coalesced dword per lane and every store instruction writes 16 B per lane
+// to 1 KB of contiguous memory. A strip's masks are one packed dword (a byte
+// per node); mask and distance dwords are byte extracts at the store. The
+// rows of the first kLeanGroup entries are loaded for the next tile before
+// this tile's compute (entries past those, sources of 5..8 tight first
+// links, are loaded in the tile), and the first tile's own bytes before the
+// entries are gathered.
+constexpr uint32_t kLeanGroup = 4;
+
+template <uint32_t Q>
+__global__ __launch_bounds__(kBlock) void first_hop_lean_kernel(HopArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  __shared__ uint32_t s_cnt;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  constexpr uint32_t kTile = kBlock * 4u * Q;
+  const uint32_t N = a.n_nodes, P = a.lvl_pitch, w0 = a.w0;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t split = a.tile_split;
+  const uint32_t lb = xcd_block(blockIdx.x, gridDim.x, a.xcd_group);
+  const uint32_t i = lb / split, phase = lb % split;
+  const uint32_t wave_at = __builtin_amdgcn_readfirstlane(tid & ~63u);  // 64 x the wave's index (its lanes' nodes: from 4 x this in a strip)
+  const uint32_t lane4 = (tid & 63u) * 4u;
+  const uint8_t* own_row = a.lvl_rows + static_cast<size_t>(i) * P;
+  // strip q of tile t starts at node t * kTile + q * 1024; this wave's part at + wave_at * 4
+  auto strip_at = [&](uint32_t tile, uint32_t q) { return tile * kTile + q * (kBlock * 4u) + wave_at * 4u; };
+  auto load_own = [&](uint32_t tile, uint32_t (&ow)[Q]) {
+#pragma unroll
+    for (uint32_t q = 0; q < Q; ++q) {
+      const uint32_t v = strip_at(tile, q) + lane4;
+      ow[q] = v < N ? *reinterpret_cast<const uint32_t*>(own_row + v) : ~0u;
+    }
+  };
+  uint32_t ow_c[Q];
+  load_own(phase, ow_c);  // in flight while the entries are gathered
+
+  // neighbour rows that may hold kLvlDirect bytes (tight or not), and the own row
+  const uint32_t nb0 = a.nbr_ptr[i], nb = a.nbr_ptr[i + 1] - nb0;
+  uint32_t redo = 0;
+  if (tid < nb) redo = a.row_deep[a.nbr_row[nb0 + tid]];
+  if (tid == kBlock - 1) redo = a.row_deep[i];
+  const uint32_t src = a.srcs[i];
+  const uint4* ent = reinterpret_cast<const uint4*>(lds + ((2 * nb + 3) & ~3u));
+  const uint32_t ne = hop_entries<true>(a, i, lds, &s_cnt);
+  // a tight link is one of metric w0 in a uniform sweep; anything else is the generic kernel's
+  if (tid < ne && ent[tid].y != w0) redo = 1;
+  if (__syncthreads_or(static_cast<int>(redo))) {
+    if (phase == 0 && tid == 0) a.redo_list[atomicAdd(a.redo_count, 1u)] = i;
+    return;
+  }
+
+  // the first kLeanGroup entries, wave-uniform: node, level row, mask bit, transit
+  uint32_t en_n[kLeanGroup], en_bit[kLeanGroup];
+  const uint8_t* en_row[kLeanGroup];
+  bool en_transit[kLeanGroup];
+#pragma unroll
+  for (uint32_t g = 0; g < kLeanGroup; ++g) {
+    en_n[g] = ~0u;
+    en_bit[g] = 0u;
+    en_row[g] = own_row;
+    en_transit[g] = false;
+    if (g < ne) {
+      const uint4 e = ent[g];
+      const uint32_t w = __builtin_amdgcn_readfirstlane(e.w);
+      en_n[g] = __builtin_amdgcn_readfirstlane(e.x);
+      en_bit[g] = 1u << (w & 7u);
+      en_row[g] = a.lvl_rows + static_cast<size_t>(__builtin_amdgcn_readfirstlane(e.z)) * P;
+      en_transit[g] = !(w >> 31);
+    }
+  }
+  auto load_nbrs = [&](uint32_t tile, uint32_t (&nx)[kLeanGroup][Q]) {
+#pragma unroll
+    for (uint32_t g = 0; g < kLeanGroup; ++g) {
+      if (!en_transit[g]) continue;
+#pragma unroll
+      for (uint32_t q = 0; q < Q; ++q) {
+        const uint32_t v = strip_at(tile, q) + lane4;
+        nx[g][q] = v < N ? *reinterpret_cast<const uint32_t*>(en_row[g] + v) : 0u;
+      }
+    }
+  };
+  // entry {node n, bit} as the first hop towards n itself: the byte of n in
+  // its strip's packed word, if n is reached (one scalar test per strip)
+  auto direct = [&](uint32_t n, uint32_t bit, uint32_t at, uint32_t reached, uint32_t& pk) {
+    if (n - at >= 256u) return;
+    const uint32_t d = n - at - lane4;
+    if (d < 4u) pk |= ((reached >> (d * 8u + 7u)) & 1u) * (bit << (d * 8u));
+  };
+
+  uint32_t nx_c[kLeanGroup][Q];
+  load_nbrs(phase, nx_c);
+  uint32_t* const nh = a.out_nh + static_cast<size_t>(i) * N;
+  uint32_t* const od = const_cast<uint32_t*>(a.dist) + static_cast<size_t>(i) * N;
+  for (uint32_t tile = phase;;) {
+    const uint32_t next = tile + split;
+    const bool more = next < a.tiles;
+    uint32_t ow_n[Q], nx_n[kLeanGroup][Q];
+#ifndef ORH_EXP_LEAN_NO_PREFETCH  // timing experiment only: the next tile's loads after this tile's stores
+    if (more) {  // the next tile's rows, before this tile's compute
+      load_own(next, ow_n);
+      load_nbrs(next, nx_n);
+    }
+#endif
+#pragma unroll
+    for (uint32_t q = 0; q < Q; ++q) {
+      const uint32_t at = strip_at(tile, q), v = at + lane4;
+      const uint32_t ow = ow_c[q];
+      const uint32_t live = lvl_reached(ow);  // 0x80 per reached node (the padding lanes: none)
+      uint32_t ot = ow, reached = live;
+      if (src - at < 256u) {  // the source's strip: its own byte counts as unreached
+        ot = lvl_own_forced(ow, src - at - lane4);
+        reached = lvl_reached(ot);
+      }
+      uint32_t pk = 0u;
+#pragma unroll
+      for (uint32_t g = 0; g < kLeanGroup; ++g) {
+        if (en_transit[g]) pk |= lvl_tight(nx_c[g][q], ot, kLvlAllReached) * en_bit[g];
+        direct(en_n[g], en_bit[g], at, reached, pk);
+      }
+      for (uint32_t e = kLeanGroup; e < ne; ++e) {  // sources of more tight links: one round trip each
+        const uint4 en = ent[e];
+        const uint32_t w = __builtin_amdgcn_readfirstlane(en.w), bit = 1u << (w & 7u);
+        if (!(w >> 31)) {
+          const uint8_t* row = a.lvl_rows + static_cast<size_t>(__builtin_amdgcn_readfirstlane(en.z)) * P;
+          const uint32_t nx = v < N ? *reinterpret_cast<const uint32_t*>(row + v) : 0u;
+          pk |= lvl_tight(nx, ot, kLvlAllReached) * bit;
+        }
+        direct(__builtin_amdgcn_readfirstlane(en.x), bit, at, reached, pk);
+      }
+      if (v >= N) continue;  // N % 4 == 0: a lane's four nodes are all inside or all outside
+      if (a.write_dist) {
+        // the source's own distance row from the level bytes (its own entry is
+        // level 0); no byte is kLvlDirect here
+        u32x4 d = {(ow & 0xFFu) * w0, ((ow >> 8) & 0xFFu) * w0, ((ow >> 16) & 0xFFu) * w0, (ow >> 24) * w0};
+        if (live != 0x80808080u) {
+          if (!(live & 0x80u)) d.x = kInf;
+          if (!(live & 0x8000u)) d.y = kInf;
+          if (!(live & 0x800000u)) d.z = kInf;
+          if (!(live & 0x80000000u)) d.w = kInf;
+        }
+        __builtin_nontemporal_store(d, reinterpret_cast<u32x4*>(od + v));
+      }
+      const u32x4 m = {pk & 0xFFu, (pk >> 8) & 0xFFu, (pk >> 16) & 0xFFu, pk >> 24};
+      __builtin_nontemporal_store(m, reinterpret_cast<u32x4*>(nh + v));
+    }
+    if (!more) break;
+#ifdef ORH_EXP_LEAN_NO_PREFETCH
+    load_own(next, ow_n);
+    load_nbrs(next, nx_n);
+#endif
+    tile = next;
+#pragma unroll
+    for (uint32_t q = 0; q < Q; ++q) {
+      ow_c[q] = ow_n[q];
+#pragma unroll
+      for (uint32_t g = 0; g < kLeanGroup; ++g) nx_c[g][q] = nx_n[g][q];
+    }
+  }
+}
+
+size_t hop_aux_bytes(uint32_t n_rows) { return (hop_aux_deep_off(n_rows) + n_rows + 255) & ~size_t{255}; }
+
 size_t hop_lds_bytes(uint32_t max_nbr) {
   return static_cast<size_t>((2 * max_nbr + 3) & ~3u) * 4 + static_cast<size_t>(max_nbr) * 16;
 }
 
 hipError_t launch_first_hop(HopArgs a, uint32_t max_nbr, hipStream_t s, uint32_t* nodes_per_thread,
-                            uint32_t* split) {
+                            uint32_t* split, uint32_t* lean_ran) {
+  if (lean_ran) *lean_ran = 0;
   if (a.n_out == 0) return hipSuccess;
   a.tiles = (a.n_nodes + kBlock * kHopPer - 1) / (kBlock * kHopPer);
   const uint64_t grid = static_cast<uint64_t>(a.tiles) * a.n_out;
@@ -395,6 +567,26 @@ hipError_t launch_first_hop(HopArgs a, uint32_t max_nbr, hipStream_t s, uint32_t
     }
     if (nodes_per_thread) *nodes_per_thread = per;
     if (split) *split = a.tile_split;
+    // The lean kernel where its preconditions hold (ORH_HOP_LEAN=0, read per
+    // launch: never). Its tile is the 8-node kernel's (256 x 4 x Q nodes, Q =
+    // 2), so tiles, tile_split, n_logical and the XCD-aware block order above
+    // are kept as they are; one workgroup per logical block. N % 4 != 0 or an
+    // unaligned output is declined (the rows of odd sources would start off a
+    // 16-byte boundary). The generic kernel follows over the sources the lean
+    // one listed - none, in a sweep of fewer than kLvlDirect levels - with at
+    // most a workgroup per CU; the search kernel emptied the list.
+    constexpr uint32_t kLeanQ = 2;
+    const bool lean = launch_knobs().hop_lean && wide && per == 4 * kLeanQ && a.words == 1 && max_nbr <= 8 &&
+                      !a.ignore_ptr && a.row_deep && a.redo_list && a.redo_count && (a.n_nodes & 3u) == 0 &&
+                      ((reinterpret_cast<uintptr_t>(a.out_nh) | reinterpret_cast<uintptr_t>(a.dist)) & 15u) == 0 &&
+                      g2 == a.n_logical;
+    if (lean_ran) *lean_ran = lean ? 1u : 0u;
+    if (lean) {
+      const hipError_t e = launch(first_hop_lean_kernel<kLeanQ>, a, a.n_logical, kBlock, lds, s);
+      if (e != hipSuccess) return e;
+      const uint32_t redo_grid = std::min(a.n_logical, n_cu ? n_cu : 256u);
+      return launch(first_hop_lvl_kernel<4 * kLeanQ, true>, a, redo_grid, kBlock, lds, s);
+    }
     return per == 16 ? launch(first_hop_lvl_kernel<16>, a, static_cast<uint32_t>(g2), kBlock, lds, s)
          : per == 8  ? launch(first_hop_lvl_kernel<8>, a, static_cast<uint32_t>(g2), kBlock, lds, s)
                      : launch(first_hop_lvl_kernel<4>, a, static_cast<uint32_t>(g2), kBlock, lds, s);
@@ -406,3 +598,8 @@ hipError_t launch_first_hop(HopArgs a, uint32_t max_nbr, hipStream_t s, uint32_t
 }
 
 }  // namespace orh
+
+// openr_hip.h: the host build of the kernels' bytewise first-hop test
+extern "C" uint32_t orh_lvl_tight_word(uint32_t nbr_word, uint32_t own_word, uint32_t src_byte) {
+  return orh::lvl_tight_word(nbr_word, own_word, src_byte);
+}

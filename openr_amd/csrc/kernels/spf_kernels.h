@@ -96,6 +96,12 @@ struct SpfArgs {
   // u16 plans): 8-byte slots {u | overloaded(u) << 31, w(u -> v)} in the
   // geometry of wsl_off / wsl_band (offsets in slots), padding {N, 0}
   const uint2* wsw_slots;
+  // multi-source BFS, for the lean first-hop kernel (nullable): row_deep[r] = 1
+  // when row r's batch searched to a level >= kLvlDirect (its level row may
+  // hold kLvlDirect bytes), else 0 - written for every row of every sweep;
+  // and the count of that kernel's redo list, which workgroup 0 zeroes
+  uint8_t* row_deep;
+  uint32_t* hop_redo_count;
 };
 
 // phase 2: first-hop masks of the requested rows from the distance rows of
@@ -136,6 +142,13 @@ struct HopArgs {
   // the level bytes it holds (the level-only ms_finalize_kernel ran before
   // it); entries marked kLvlDirect stay as the search kernel wrote them
   uint32_t write_dist;
+  // lean level-row kernel (first_hop_lean_kernel): SpfArgs::row_deep, and the
+  // sources it leaves to first_hop_lvl_kernel's list entry - a source whose
+  // own row or a neighbour's row may hold kLvlDirect bytes. *redo_count is
+  // zeroed by the search kernel of the same sweep
+  const uint8_t* row_deep;
+  uint32_t* redo_list;   // [n_out]
+  uint32_t* redo_count;
 };
 
 enum class SpfVariant {
@@ -272,9 +285,17 @@ size_t ms_log_bytes(const SpfPlan& plan, uint32_t n_rows);
 // LDS bytes the first-hop kernel needs for max_nbr distinct neighbours
 size_t hop_lds_bytes(uint32_t max_nbr);
 // *nodes_per_thread / *split receive the chosen kernel shape (16 or 4 nodes
-// per thread over level rows, 1 for u32 rows)
+// per thread over level rows, 1 for u32 rows); *lean: 1 when the lean
+// level-row kernel ran (then a launch of the generic kernel over its redo
+// list follows it on the stream)
 hipError_t launch_first_hop(HopArgs a, uint32_t max_nbr, hipStream_t s,
-                            uint32_t* nodes_per_thread = nullptr, uint32_t* split = nullptr);
+                            uint32_t* nodes_per_thread = nullptr, uint32_t* split = nullptr,
+                            uint32_t* lean = nullptr);
+// bytes of the lean kernel's per-sweep state for n_rows rows: redo count,
+// redo list, row_deep flags (hop_aux_* give the offsets)
+size_t hop_aux_bytes(uint32_t n_rows);
+inline size_t hop_aux_list_off() { return 16; }
+inline size_t hop_aux_deep_off(uint32_t n_rows) { return 16 + static_cast<size_t>(n_rows) * 4; }
 // multi-source BFS plans, phase 2a: node-major level bytes -> requested dist
 // rows (host order) and u8 level rows of every row (a.lvl_rows), which the
 // first-hop phase reads instead of u32 distance rows. write_dist = false: the

@@ -21,6 +21,8 @@ struct LaunchKnobs {
   bool wms_four;        // ORH_WMS_SOURCES=4 (A/B): 4-source batches even where 8 fit
   bool wms_wide_two;    // ORH_WMS_WIDE_SOURCES=2 (A/B): 2-source wide batches even where 4 fit
   bool hop_xcd;         // ORH_HOP_XCD=1 (A/B): first_hop_kernel's XCD-aware source order
+  bool hop_lean;        // ORH_HOP_LEAN=0 (A/B): the generic level-row first-hop kernel even where the
+                        // lean one applies
   // read once per process
   uint32_t lds16_block;  // ORH_LDS16_BLOCK (A/B): threads per u16 LDS search (one search per CU
                          // either way); a multiple of 64 in [64, 1024], else 1024

@@ -260,7 +260,8 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
   // trip a level, not two)
   uint32_t act = 0u;
   if constexpr (kAdj) act = s_act[0][lane & 7u];
-  for (uint32_t level = 1;; ++level) {
+  uint32_t level = 1;
+  for (;; ++level) {
     int prog = 0;
     // opaque per level: keeps the compiler from hoisting J * K unpacked LDS
     // addresses and J per-node pointers out of the level loop (VGPR budget:
@@ -431,6 +432,12 @@ __global__ __launch_bounds__(1024) void spf_msbfs_kernel(SpfArgs a) {
     cur_off = nxt_off;
     nxt_off = to;
   }
+  // for the lean first-hop kernel: the rows of this batch may hold kLvlDirect
+  // bytes iff its last level with an arrival (level - 1) got that far; every
+  // output path below shares this one store. Workgroup 0 also empties that
+  // kernel's redo list
+  if (a.row_deep && tid < S) a.row_deep[a.order[b0 + tid]] = level > kLvlDirect ? 1u : 0u;
+  if (a.hop_redo_count && blockIdx.x == 0 && tid == 0) *a.hop_redo_count = 0u;
   if constexpr (kLog) {
     // the logs -> node-major level blocks, one wave's nodes at a time: the
     // workgroup zeroes their J * 64 blocks in LDS (the frontier arrays are

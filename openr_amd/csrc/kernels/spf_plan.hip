@@ -42,6 +42,8 @@ LaunchKnobs launch_knobs() {
   k.wms_wide_two = e && atoi(e) == 2;
   e = getenv("ORH_HOP_XCD");
   k.hop_xcd = e && e[0] == '1';
+  e = getenv("ORH_HOP_LEAN");
+  k.hop_lean = !(e && e[0] == '0');
   return k;
 }
 

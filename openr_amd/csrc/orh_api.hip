@@ -49,6 +49,10 @@ struct orh_ctx {
   // multi-source BFS: u8 level row per row (first-hop input)
   uint8_t* d_lvl_rows = nullptr;
   size_t d_lvl_rows_cap = 0;  // in bytes
+  // lean first-hop kernel: per half (p2_half) redo count, redo list and
+  // row_deep flags (orh::hop_aux_bytes)
+  uint8_t* d_hop_aux = nullptr;
+  size_t d_hop_aux_cap = 0;  // in bytes, both halves
   // multi-source BFS: node-major level bytes
   uint8_t* d_ms_lvl = nullptr;
   size_t d_ms_lvl_cap = 0;
@@ -773,6 +777,17 @@ int ensure_lvl_rows(orh_ctx* ctx, size_t bytes) {
   return ORH_OK;
 }
 
+int ensure_hop_aux(orh_ctx* ctx, size_t bytes) {
+  if (bytes <= ctx->d_hop_aux_cap) return ORH_OK;
+  drain_deferred(ctx);
+  hipFree(ctx->d_hop_aux);
+  ctx->d_hop_aux = nullptr;
+  ctx->d_hop_aux_cap = 0;
+  ORH_HIP(ctx, hipMalloc(&ctx->d_hop_aux, bytes));
+  ctx->d_hop_aux_cap = bytes;
+  return ORH_OK;
+}
+
 int ensure_labels(orh_ctx* ctx, size_t n) {
   if (n <= ctx->d_labels_cap) return ORH_OK;
   hipFree(ctx->d_labels);
@@ -911,6 +926,7 @@ int orh_destroy(orh_ctx* ctx) {
   hipFree(ctx->d_scratch);
   hipFree(ctx->d_labels);
   hipFree(ctx->d_lvl_rows);
+  hipFree(ctx->d_hop_aux);
   hipFree(ctx->d_ms_lvl);
   hipFree(ctx->d_batch);
   hipFree(ctx->d_patch);
@@ -2529,6 +2545,14 @@ int fill_spf_args(orh_graph* g, const SweepFacts& f, const SweepPlan& sp, const 
     rc = ensure_lvl_rows(ctx, static_cast<size_t>(sp.n_rows) * a.lvl_pitch);
     if (rc) return rc;
     a.lvl_rows = ctx->d_lvl_rows;
+    // the lean first-hop kernel's state: a deferred phase 2 reads its half
+    // while the next sweep's search writes the other
+    const size_t aux = orh::hop_aux_bytes(sp.n_rows);
+    rc = ensure_hop_aux(ctx, 2 * aux);
+    if (rc) return rc;
+    uint8_t* half = ctx->d_hop_aux + (*defer ? ctx->p2_half * aux : 0);
+    a.hop_redo_count = reinterpret_cast<uint32_t*>(half);
+    a.row_deep = half + orh::hop_aux_deep_off(sp.n_rows);
   }
   a.order = g->d_req + (sp.run.variant == V::kMsBfs ? st.off_order_ms : st.off_order);
   a.srcs = g->d_req + 1;
@@ -2601,6 +2625,11 @@ orh::HopArgs fill_hop_args(const orh_graph* g, const SweepFacts& f, const SweepP
   h.lvl_rows = sp.run.variant == orh::SpfVariant::kMsBfs ? a.lvl_rows : nullptr;
   h.lvl_pitch = a.lvl_pitch;
   h.w0 = f.w0;
+  if (h.lvl_rows && a.row_deep) {
+    h.row_deep = a.row_deep;
+    h.redo_count = a.hop_redo_count;
+    h.redo_list = a.hop_redo_count + orh::hop_aux_list_off() / 4;
+  }
   return h;
 }
 
@@ -2781,8 +2810,9 @@ int launch_phase2(orh_graph* g, const SweepPlan& sp, const SpfKnobs& k, const or
       if (e != hipSuccess) return hip_fail(ctx, e, "multi-source finalize launch");
     }
   }
-  const hipError_t e = orh::launch_first_hop(h, max_nbr, *end, &info->hop_nodes, &info->hop_split);
+  const hipError_t e = orh::launch_first_hop(h, max_nbr, *end, &info->hop_nodes, &info->hop_split, &info->hop_lean);
   if (e != hipSuccess) return hip_fail(ctx, e, "first-hop kernel launch");
+  info->hop_redo = info->hop_lean ? h.n_out : 0u;
   if (defer) {
     ORH_HIP(ctx, hipEventRecord(ctx->ev_p2[ctx->p2_half], *end));
     ctx->p2_pending[ctx->p2_half] = true;
