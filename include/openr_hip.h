@@ -322,14 +322,20 @@ int orh_spf_batch_exact(orh_graph* g, const orh_spf_request* req, uint32_t words
 #define ORH_GRAPH_WIDE_METRIC 2u /* link-metric path sums can reach 2^32 - 1 */
 int orh_graph_flags(const orh_graph* g, uint32_t* flags);
 
-/* ---- what-if jobs (batched link-failure SPFs) ---------------------------
+/* ---- what-if jobs (batched link-failure and node-drain SPFs) ------------
  * runSpf(src, useLinkMetric, linksToIgnore) (LinkState.cpp:808-882) for many
  * (source, ignore set) requests over a fixed source set - the C4 shape,
  * "4,096 links x 64 sources" (SURVEY.md §8d). orh_whatif_create searches the
  * plain rows of its sources once; every orh_whatif_run derives its requests'
  * rows from them: a request's row is its source's row except below a tight
  * ignored link, where it is re-derived (results are bit-identical to a fresh
- * runSpf). A job is bound to the graph structure it was created on
+ * runSpf). orh_whatif_run_drains adds, per request, a set of drained nodes:
+ * nodes treated as if their overload bit were set
+ * (LinkState::updateNodeOverloaded, LinkState.cpp:480-493), which stay
+ * reachable but carry no transit traffic (:831-838). A drain removes only the
+ * relaxations out of the node, so the same repair covers it: the rows change
+ * only below the node's tight out-links, and are as exact.
+ * A job is bound to the graph structure it was created on
  * (ORH_E_STATE after a delta or reload). Everything is asynchronous on the
  * context stream; one mask word per node (every source has <= 32 distinct
  * neighbours), no zero-metric links (ORH_E_UNSUPPORTED otherwise). */
@@ -344,6 +350,17 @@ int orh_whatif_create(orh_graph* g, const uint32_t* h_srcs, uint32_t n_srcs, int
  * Host arrays may be reused once the call returns. */
 int orh_whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
                    const uint32_t* h_ignore_links, uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info);
+/* orh_whatif_run with, per request, a set of nodes treated as overloaded
+ * (drained): request i = runSpf(src_i, use_link_metric, ignore_i) on the graph
+ * with isOverloaded set on h_drain_nodes[h_drain_ptr[i] .. h_drain_ptr[i+1])
+ * (graph node ids). h_drain_ptr == NULL: exactly orh_whatif_run. A set may be
+ * empty, repeat nodes, and name the request's source (which still relaxes),
+ * or nodes that are overloaded already, unreached or isolated (no-ops); a
+ * node id >= N is ORH_E_INVALID, returned before anything is queued. */
+int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx,
+                          const uint32_t* h_ignore_ptr, const uint32_t* h_ignore_links,
+                          const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
+                          uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info);
 #define ORH_WHATIF_TIER(x) ((x) & 7u) /* 0 source row, 1/2 LDS repair, 3 global-slot repair, 4 full search
                                          (subtrees too large for LDS, up to ORH_WHATIF_FULL per run; every
                                          such request without slots) */

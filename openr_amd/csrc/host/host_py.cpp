@@ -895,11 +895,14 @@ PYBIND11_MODULE(_openr_host, m) {
       .def("what_if_batch",  // a what-if job over `srcs`: request i = (srcs[src_idx[i]], ignore[i])
            [](const LinkState& s, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric,
-              bool shareBase, bool searchLarge) {
-             return new WhatIfBatch(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase, searchLarge);
+              bool shareBase, bool searchLarge, const std::optional<std::vector<std::vector<std::string>>>& drain) {
+             // drain: per request the node names it treats as overloaded (None: no drains)
+             return new WhatIfBatch(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase, searchLarge,
+                                    drain ? *drain : std::vector<std::vector<std::string>>{});
            },
            py::arg("srcs"), py::arg("src_idx"), py::arg("ignore"), py::arg("chunk") = 4096,
            py::arg("use_link_metric") = true, py::arg("share_base") = false, py::arg("search_large") = false,
+           py::arg("drain") = py::none(),
            py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
       .def("run_spf_batch",
            [](const LinkState& s, const std::vector<std::string>& srcs,
@@ -995,11 +998,12 @@ PYBIND11_MODULE(_openr_host, m) {
       .def("what_if_batch",
            [](const ReplicatedLinkState& s, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric,
-              bool shareBase) {
-             return new MultiDeviceWhatIf(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase);
+              bool shareBase, const std::optional<std::vector<std::vector<std::string>>>& drain) {
+             return new MultiDeviceWhatIf(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase,
+                                          drain ? *drain : std::vector<std::vector<std::string>>{});
            },
            py::arg("srcs"), py::arg("src_idx"), py::arg("ignore"), py::arg("chunk") = 4096,
-           py::arg("use_link_metric") = true, py::arg("share_base") = false,
+           py::arg("use_link_metric") = true, py::arg("share_base") = false, py::arg("drain") = py::none(),
            py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
       .def("kth_paths_batch",
            [](const ReplicatedLinkState& s, const std::vector<std::pair<std::string, std::string>>& pairs) {

@@ -241,9 +241,12 @@ void MultiDeviceSweep::gather(uint32_t* dist, uint32_t* nh) const {
 MultiDeviceWhatIf::MultiDeviceWhatIf(const ReplicatedLinkState& rls, const std::vector<std::string>& srcs,
                                      const std::vector<uint32_t>& srcIdx,
                                      const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk,
-                                     bool useLinkMetric, bool shareBase)
+                                     bool useLinkMetric, bool shareBase,
+                                     const std::vector<std::vector<std::string>>& drain)
     : total_(srcIdx.size()) {
   if (srcIdx.size() != ignore.size()) throw std::invalid_argument("MultiDeviceWhatIf: one ignore set per request");
+  if (!drain.empty() && drain.size() != srcIdx.size())
+    throw std::invalid_argument("MultiDeviceWhatIf: one drain set per request (or none at all)");
   const size_t world = rls.replicas();
   // link ids name the same link on every replica (the same updates applied
   // in the same order); check the cheap invariant
@@ -272,11 +275,13 @@ MultiDeviceWhatIf::MultiDeviceWhatIf(const ReplicatedLinkState& rls, const std::
     std::vector<std::string> bs(srcs.begin() + static_cast<ptrdiff_t>(b.lo), srcs.begin() + static_cast<ptrdiff_t>(b.hi));
     std::vector<uint32_t> bi;
     std::vector<std::vector<uint32_t>> bg;
+    std::vector<std::vector<std::string>> bd;
     bi.reserve(b.reqs.size());
     bg.reserve(b.reqs.size());
     for (size_t i : b.reqs) {
       bi.push_back(static_cast<uint32_t>(srcIdx[i] - b.lo));
       bg.push_back(ignore[i]);
+      if (!drain.empty()) bd.push_back(drain[i]);  // each block its own requests' drains
     }
     // blocks of a 4-way or wider split are short jobs: their largest repairs
     // are searched in full (ORH_WHATIF_SEARCH_LARGE; rehearsal at 8 blocks:
@@ -290,7 +295,7 @@ MultiDeviceWhatIf::MultiDeviceWhatIf(const ReplicatedLinkState& rls, const std::
     const uint32_t n = static_cast<uint32_t>(b.reqs.size());
     const uint32_t bchunk = std::max<uint32_t>(1, std::min(chunk, (n + minChunks - 1) / minChunks));
     b.job = std::make_unique<WhatIfBatch>(rls.replica(r), bs, bi, bg, bchunk, useLinkMetric, shareBase,
-                                          world >= kSearchLargeBlocks);
+                                          world >= kSearchLargeBlocks, bd);
   }
 }
 

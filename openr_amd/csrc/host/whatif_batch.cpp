@@ -18,9 +18,20 @@ void check(orh_ctx* ctx, int rc, const char* what) {
 
 WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& srcs,
                          const std::vector<uint32_t>& srcIdx, const std::vector<std::vector<uint32_t>>& ignore,
-                         uint32_t chunk, bool useLinkMetric, bool shareBase, bool searchLarge)
+                         uint32_t chunk, bool useLinkMetric, bool shareBase, bool searchLarge,
+                         const std::vector<std::vector<std::string>>& drain)
     : ls_(ls), useLinkMetric_(useLinkMetric), shareBase_(shareBase), searchLarge_(searchLarge) {
   if (srcIdx.size() != ignore.size()) throw std::invalid_argument("WhatIfBatch: one ignore set per request");
+  if (!drain.empty() && drain.size() != srcIdx.size())
+    throw std::invalid_argument("WhatIfBatch: one drain set per request (or none at all)");
+  std::vector<std::vector<uint32_t>> drainIds(drain.size());
+  for (size_t i = 0; i < drain.size(); ++i)
+    for (const auto& name : drain[i]) {
+      auto id = ls.nodeId(name);
+      if (!id) throw std::invalid_argument("WhatIfBatch: unknown drained node " + name);
+      drainIds[i].push_back(*id);
+      drains_ = true;
+    }
   if (chunk == 0) throw std::invalid_argument("WhatIfBatch: chunk must be positive");
   for (const auto& s : srcs) {
     auto id = ls.nodeId(s);
@@ -35,13 +46,21 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
   chunk_ = static_cast<uint32_t>(std::min<size_t>(chunk, std::max<size_t>(n, 1)));
   for (size_t c0 = 0; c0 < n; c0 += chunk_) {
     const size_t c1 = std::min(n, c0 + chunk_);
-    std::vector<uint32_t> ptr{0}, links;
+    std::vector<uint32_t> ptr{0}, links, dptr, dnodes;
     for (size_t i = c0; i < c1; ++i) {
       links.insert(links.end(), ignore[i].begin(), ignore[i].end());
       ptr.push_back(static_cast<uint32_t>(links.size()));
     }
     if (links.empty()) links.push_back(0);  // non-null pointer
-    chunks_.push_back({c0, c1, std::move(ptr), std::move(links)});
+    if (drains_) {
+      dptr.push_back(0);
+      for (size_t i = c0; i < c1; ++i) {
+        dnodes.insert(dnodes.end(), drainIds[i].begin(), drainIds[i].end());
+        dptr.push_back(static_cast<uint32_t>(dnodes.size()));
+      }
+      if (dnodes.empty()) dnodes.push_back(0);
+    }
+    chunks_.push_back({c0, c1, std::move(ptr), std::move(links), std::move(dptr), std::move(dnodes)});
   }
   graph_ = ls.deviceGraph();
   ctx_ = ls.context();
@@ -132,10 +151,16 @@ void WhatIfBatch::run() {
     const Chunk& ch = chunks_[c];
     const uint32_t nr = static_cast<uint32_t>(ch.hi - ch.lo);
     const int b = static_cast<int>(c % nBuf_);  // cycle the row buffers
-    check(ctx_,
-          orh_whatif_run(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(), dDist_[b], dNh_[b],
-                         dInfo_ + ch.lo),
-          "orh_whatif_run");
+    if (drains_)
+      check(ctx_,
+            orh_whatif_run_drains(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(),
+                                  ch.drnPtr.data(), ch.drnNodes.data(), dDist_[b], dNh_[b], dInfo_ + ch.lo),
+            "orh_whatif_run_drains");
+    else
+      check(ctx_,
+            orh_whatif_run(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(), dDist_[b], dNh_[b],
+                           dInfo_ + ch.lo),
+            "orh_whatif_run");
     if (digests_) {  // the chunk's rows complete in stream order, then digested
       check(ctx_, orh_whatif_flush(job_), "orh_whatif_flush");
       check(ctx_, orh_row_digest(ctx_, dDist_[b], dNh_[b], 1, n_, nr, dDigest_ + ch.lo), "orh_row_digest");

@@ -1,9 +1,11 @@
-// Batched link-failure what-if SPFs ("4,096 links x 64
-// sources" of runSpf(src, true, {link}), LinkState.cpp:808-882) through one
+// Batched link-failure and node-drain what-if SPFs ("4,096
+// links x 64 sources" of runSpf(src, true, {link}), LinkState.cpp:808-882;
+// a drain is the same SPF with the node's overload bit set, :480-493) through one
 // what-if job of libopenr_hip (orh_whatif_*): the sources' plain rows are
 // searched once, then the requests run in chunks into device row buffers; a
-// request's row is its source's row except below a tight ignored link, where
-// the job re-derives it (bit-identical to a fresh runSpf).
+// request's row is its source's row except below a tight ignored link or a
+// tight out-link of a drained node, where the job re-derives it (bit-identical
+// to a fresh runSpf).
 //
 // This is the library form a caller outside Python drives (the bench, the
 // multi-device split in multi_device.h); the Python binding wraps it.
@@ -23,10 +25,14 @@ class WhatIfBatch {
   // ids; chunk = requests per orh_whatif_run. shareBase: ORH_WHATIF_SHARE_BASE
   // (a request whose source row stands references the job's base row);
   // searchLarge: ORH_WHATIF_SEARCH_LARGE (the largest repairs searched in
-  // full: for a device's block of a split job)
+  // full: for a device's block of a split job). drain: per request the names
+  // of the nodes it treats as overloaded (empty: no request drains any; else
+  // one list per request, each possibly empty); an unknown name is
+  // std::invalid_argument
   WhatIfBatch(const LinkState& ls, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric = true,
-              bool shareBase = false, bool searchLarge = false);
+              bool shareBase = false, bool searchLarge = false,
+              const std::vector<std::vector<std::string>>& drain = {});
   ~WhatIfBatch();
   WhatIfBatch(const WhatIfBatch&) = delete;
   WhatIfBatch& operator=(const WhatIfBatch&) = delete;
@@ -62,6 +68,7 @@ class WhatIfBatch {
   struct Chunk {
     size_t lo, hi;
     std::vector<uint32_t> ptr, links;
+    std::vector<uint32_t> drnPtr, drnNodes;  // drained node ids, rebased like the ignore CSR
   };
   void allocate();
   const LinkState& ls_;
@@ -69,6 +76,7 @@ class WhatIfBatch {
   bool shareBase_;
   bool searchLarge_;
   bool digests_{false};
+  bool drains_{false};  // some request drains a node: runs go through orh_whatif_run_drains
   std::vector<uint32_t> srcs_, srcIdx_;
   std::vector<Chunk> chunks_;
   uint32_t chunk_{1};

@@ -72,6 +72,19 @@ __device__ inline bool ignored(const uint32_t* ign, uint32_t n, uint32_t link) {
   return false;
 }
 
+// is `node` in the request's drain set (what-if jobs: nodes treated as
+// overloaded)? sorted ascending, a few entries; callers test n != 0 first
+__device__ inline bool drained(const uint32_t* drn, uint32_t n, uint32_t node) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    const uint32_t x = drn[mid];
+    if (x == node) return true;
+    if (x < node) lo = mid + 1; else hi = mid;
+  }
+  return false;
+}
+
 __device__ inline uint32_t* dist_row(uint32_t* out, uint32_t* scratch, uint32_t n_out, uint32_t N,
                                      uint32_t row) {
   return row < n_out ? out + static_cast<size_t>(row) * N
@@ -115,8 +128,12 @@ struct Src {
   // false negatives): a clear bit skips the binary search in global memory
   const uint32_t* filt;
   uint32_t fshift;
+  // the row's drained nodes (SpfArgs::drain_ptr); set by the kernel
+  // instantiation that honours them (spf_global_nh_async_kernel, kDrain)
+  const uint32_t* drn;
+  uint32_t n_drn;
   __device__ Src(const SpfArgs& a, uint32_t row)
-      : node(a.srcs[row]), ign(nullptr), n_ign(0), filt(nullptr), fshift(0) {
+      : node(a.srcs[row]), ign(nullptr), n_ign(0), filt(nullptr), fshift(0), drn(nullptr), n_drn(0) {
     if (a.ignore_ptr) {
       const uint32_t b = a.ignore_ptr[row];
       ign = a.ignore_links + b;

@@ -46,7 +46,8 @@ struct NoPre {
 // the most pushes the group can make (its records, continuation lists
 // included); a caller that passes one calls expand_group from every lane
 // (c = 0 included), so pre runs with the whole wave active
-template <int K, int G, typename L, typename Merge, typename Pre = NoPre>
+// kDrain: the row's drained nodes (s.drn, what-if jobs) are no transit either
+template <int K, int G, typename L, bool kDrain, typename Merge, typename Pre = NoPre>
 __device__ __forceinline__ void expand_group(const SpfArgs& a, const Src& s, L* lab,
                                              const uint32_t (&vs)[G], int c, Merge& merge,
                                              Pre&& pre = Pre{}) {
@@ -73,7 +74,8 @@ __device__ __forceinline__ void expand_group(const SpfArgs& a, const Src& s, L* 
   bool ok[G][K];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    const bool transit = g < c && (vs[g] == s.node || !(rec[g][0].x & ORH_REC_ROW_OVL));
+    bool transit = g < c && (vs[g] == s.node || !(rec[g][0].x & ORH_REC_ROW_OVL));
+    if constexpr (kDrain) transit = transit && !(s.n_drn && vs[g] != s.node && drained(s.drn, s.n_drn, vs[g]));
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       ok[g][j] = transit && live_link(s, rec[g][j], lk[g][j]);
@@ -87,6 +89,8 @@ __device__ __forceinline__ void expand_group(const SpfArgs& a, const Src& s, L* 
     if (g >= c) break;
     const uint32_t v = vs[g];
     if (v != s.node && (rec[g][0].x & ORH_REC_ROW_OVL)) continue;  // no transit
+    if constexpr (kDrain)
+      if (s.n_drn && v != s.node && drained(s.drn, s.n_drn, v)) continue;  // drained: no transit
     const uint32_t dv = lab_dist(lv[g]);
     const uint32_t nhv = lab_nh(lv[g]);
     const bool from_src = kNh && v == s.node;
@@ -124,7 +128,9 @@ __device__ __forceinline__ void expand_group(const SpfArgs& a, const Src& s, L* 
 // rounds); what goes away is the per-round barrier that held every wave to
 // the slowest one (the C4 WAN runs about a hundred near rounds per search:
 // the C4 what-if 2.39 -> 2.05 ms, profiles/r02/p_hbm_async_ab.txt).
-template <int K, bool kNh>
+// kDrain (what-if jobs with drained nodes, a.drain_ptr set): the row's drain
+// set counts as overloaded; the other launches run the instantiation without
+template <int K, bool kNh, bool kDrain>
 __global__ __launch_bounds__(1024) void spf_global_nh_async_kernel(SpfArgs a) {
   typedef typename std::conditional<kNh, unsigned long long, uint32_t>::type L;
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -142,6 +148,10 @@ __global__ __launch_bounds__(1024) void spf_global_nh_async_kernel(SpfArgs a) {
   uint32_t* far = lds + NB;
   if (a.row_mask && !a.row_mask[row]) return;  // repaired elsewhere (whole workgroup)
   Src s(a, row);
+  if constexpr (kDrain) {
+    s.drn = a.drain_nodes + a.drain_ptr[row];
+    s.n_drn = a.drain_ptr[row + 1] - a.drain_ptr[row];
+  }
   L* lab = reinterpret_cast<L*>(a.labels) + static_cast<size_t>(a.row_list ? blockIdx.x : row) * N;
   // the plan's third bitmap holds the ignore filter: FW words, a power of two
   // <= 256, and the set's real length (fixed-stride lists end in ~0u padding,
@@ -241,7 +251,7 @@ __global__ __launch_bounds__(1024) void spf_global_nh_async_kernel(SpfArgs a) {
       // the expanded nodes returned after them
       uint32_t bound = 0;
       newq = 0;
-      expand_group<K, G, L>(a, s, lab, vs, c, merge, [&](uint32_t b) {
+      expand_group<K, G, L, kDrain>(a, s, lab, vs, c, merge, [&](uint32_t b) {
         bound = b;
         const uint32_t r = wave_sum(b);
         if ((tid & 63u) == 0u && r) atomicAdd(&s_work, r);
@@ -301,9 +311,13 @@ __global__ __launch_bounds__(1024) void spf_global_nh_async_kernel(SpfArgs a) {
 
 template <int K>
 static hipError_t launch_global_nh_k(const SpfPlan& plan, const SpfArgs& a, uint32_t n_rows, hipStream_t s) {
-  if (a.dist_only)  // distances alone (u32 labels), no first-hop rows
-    return launch(spf_global_nh_async_kernel<K, false>, a, n_rows, plan.block, plan.lds_bytes, s);
-  return launch(spf_global_nh_async_kernel<K, true>, a, n_rows, plan.block, plan.lds_bytes, s);
+  if (a.dist_only) {  // distances alone (u32 labels), no first-hop rows
+    if (a.drain_ptr) return hipErrorInvalidValue;  // drains come with first hops (what-if jobs)
+    return launch(spf_global_nh_async_kernel<K, false, false>, a, n_rows, plan.block, plan.lds_bytes, s);
+  }
+  if (a.drain_ptr)
+    return launch(spf_global_nh_async_kernel<K, true, true>, a, n_rows, plan.block, plan.lds_bytes, s);
+  return launch(spf_global_nh_async_kernel<K, true, false>, a, n_rows, plan.block, plan.lds_bytes, s);
 }
 
 hipError_t launch_global_nh(const SpfPlan& plan, const SpfArgs& a, uint32_t n_rows, hipStream_t s) {

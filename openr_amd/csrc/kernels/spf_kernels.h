@@ -102,6 +102,11 @@ struct SpfArgs {
   // and the count of that kernel's redo list, which workgroup 0 zeroes
   uint8_t* row_deep;
   uint32_t* hop_redo_count;
+  // HBM kernel with fused first hops (nullable: none): row r treats the nodes
+  // drain_nodes[drain_ptr[r] .. drain_ptr[r + 1]) (sorted, never the row's
+  // source) as overloaded - the what-if job's drained nodes
+  const uint32_t* drain_ptr;  // [n_rows + 1]
+  const uint32_t* drain_nodes;
 };
 
 // phase 2: first-hop masks of the requested rows from the distance rows of

@@ -20,6 +20,8 @@ namespace orh {
 //   tier 2 large LDS state (cap_a / cap_e)
 //   tier 3 global slots sized for the whole graph (cannot overflow)
 //   tier 4 only without slots: the full HBM search (fallback flags)
+// A request may also drain nodes (treat them as overloaded): their
+// out-records are staged as cuts, drn_ptr / drn carry the sets.
 constexpr uint32_t kWhatifTierBase = 0, kWhatifTierSmall = 1, kWhatifTierLarge = 2, kWhatifTierSlot = 3,
                    kWhatifTierSearch = 4;
 constexpr uint32_t kSmallA = 256, kSmallE = 1024;
@@ -45,7 +47,13 @@ struct RepairArgs {
   const uint32_t* ign_ptr;    // [n_req + 1]
   const uint32_t* ign;        // sorted per request
   const uint32_t* cut_ptr;    // [n_req + 1]
-  const uint4* cuts;          // (tail, head, record tail -> head, 0) per ignored link end
+  const uint4* cuts;          // (tail, head, record tail -> head, 0) per ignored link end, and per
+                              // out-record of a drained node
+  // drained nodes (nullable: none, and the kernels without the drain tests
+  // run): per request the nodes treated as overloaded, sorted, without the
+  // request's source
+  const uint32_t* drn_ptr;    // [n_req + 1]
+  const uint32_t* drn;
   uint32_t* out_dist;         // [n_req][N]
   uint32_t* out_nh;           // [n_req][N], one mask word
   uint32_t* fallback;         // [n_req] set when a request needs the full search (no slots)

@@ -34,6 +34,27 @@
 //                         slots run out re-searched by
 //                         spf_global_nh_async_kernel with the flags as its
 //                         row mask
+//
+// Drained nodes (orh_whatif_run_drains): a request may also name nodes to be
+// treated as overloaded. Draining X (not the source, reached, not already
+// overloaded) removes exactly the relaxations out of X, so it is a link cut in
+// one direction only: the host stages one cut (X, y, record X -> y) per
+// out-record of X and the seeds take them as they are. A then is
+//
+//   the heads of the tight ignored links and of the tight out-records of the
+//   drained nodes, closed under tight out-records of transit nodes that are
+//   not drained in this request
+//
+// (a drained node inside A is re-derived but not expanded: its own tight
+// heads are seeds already), and the predecessor rule skips a drained
+// predecessor p != s as it skips an overloaded one. The lattice argument is
+// unchanged: relaxations are only removed, a node outside A keeps all of its
+// tight predecessors (none is in A, none drained with a tight record to it,
+// since that record's head would be a seed), and inside A the fixpoint over
+// the remaining predecessor edges is unique. The repair kernels are
+// instantiated with and without the drain tests (kDrain); a run without
+// drains launches the code it always did. Tier 4's full search honours the
+// set through SpfArgs::drain_ptr (spf_hbm_kernels.hip, its own kDrain).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -125,7 +146,7 @@ __global__ __launch_bounds__(256) void whatif_copy_kernel(RepairArgs a, uint32_t
 // caps cap_a / cap_e (LDS, or a global slot with whole-graph caps). Returns
 // |A|, or ~0u when A or its edge list outgrows the caps. The membership
 // bitmap must be all zero on entry; the caller clears it afterwards.
-template <int K>
+template <int K, bool kDrain>
 __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, uint32_t cap_a, uint32_t cap_e,
                                uint32_t* s_cnt, uint32_t* s_ecnt, uint32_t* s_ovf, uint32_t* s_flag) {
   const uint32_t N = a.n_nodes;
@@ -148,6 +169,13 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
   const uint32_t* ign = a.ign + a.ign_ptr[r];
   const uint32_t n_ign = a.ign_ptr[r + 1] - a.ign_ptr[r];
   const bool metric = a.use_link_metric != 0;
+  // the request's drained nodes (sorted; never s): no transit, like ovl
+  const uint32_t* drn = nullptr;
+  uint32_t n_drn = 0;
+  if constexpr (kDrain) {
+    drn = a.drn + a.drn_ptr[r];
+    n_drn = a.drn_ptr[r + 1] - a.drn_ptr[r];
+  }
 
   if (tid == 0) {
     *s_cnt = 0u;
@@ -164,7 +192,8 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
     if (k < cap_a) alist[k] = u;
     else *s_ovf = 1u;
   };
-  // seeds: heads of tight ignored records whose tail is a transit node
+  // seeds: heads of tight ignored records whose tail is a transit node (a
+  // drained node's out-records are staged as cuts of their own)
   for (uint32_t c = a.cut_ptr[r] + tid; c < a.cut_ptr[r + 1]; c += B) {
     const uint4 cut = a.cuts[c];  // (tail, head, record of tail -> head, 0)
     const uint2 rec = a.recs[cut.z];
@@ -186,6 +215,8 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
     for (uint32_t k = lo + tid; k < hi; k += B) {
       const uint32_t v = alist[k];
       if (a.ovl[v]) continue;  // reached, but no transit (v != s: s is never in A)
+      if constexpr (kDrain)
+        if (n_drn && drained(drn, n_drn, v)) continue;  // re-derived, not expanded
       const uint64_t dv = bd[v];
       for_records<K>(a.recs, v, [&](const uint2& rec, uint32_t) {
         const uint32_t u = rec.x & ORH_REC_COL_MASK;
@@ -209,6 +240,8 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
     const uint32_t q2 = a.rev[q];
     const uint2 back = a.recs[q2];  // p -> v: p's metric and p's overload bit
     if (p != s && (back.x & ORH_REC_ROW_OVL)) return;
+    if constexpr (kDrain)
+      if (n_drn && p != s && drained(drn, n_drn, p)) return;
     const uint32_t w = metric ? back.y : 1u;
     if (bits[p >> 5] & (1u << (p & 31u))) inside(p, w);
     else outside(p, q2, w);
@@ -322,7 +355,7 @@ __global__ __launch_bounds__(256) void whatif_seed_kernel(RepairArgs a) {
 // slot per workgroup (tier 3); a request that outgrows the caps moves on to
 // the next queue. Every workgroup leaves once its claim passes the queue's
 // length (fixed before this launch by the previous kernel).
-template <int K, uint32_t kTier>
+template <int K, uint32_t kTier, bool kDrain>
 __global__ __launch_bounds__(kTier == kWhatifTierSmall ? 128 : kTier == kWhatifTierLarge ? 256 : kSlotBlock)
 void whatif_repair_kernel(RepairArgs a, uint32_t cap_a, uint32_t cap_e, uint32_t q) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -348,7 +381,7 @@ void whatif_repair_kernel(RepairArgs a, uint32_t cap_a, uint32_t cap_e, uint32_t
     bar();
     const uint32_t r = s_req;
     if (r == ~0u) break;
-    const uint32_t n = repair_one<K>(a, r, base, cap_a, cap_e, &s_cnt, &s_ecnt, &s_ovf, s_flag);
+    const uint32_t n = repair_one<K, kDrain>(a, r, base, cap_a, cap_e, &s_cnt, &s_ecnt, &s_ovf, s_flag);
     if (tid == 0) {
       if (n != ~0u) {
         if (a.info) a.info[r] = kTier | (n << 3);
@@ -420,6 +453,24 @@ hipError_t launch_repair_back(const RepairArgs& a, uint32_t ell_k, size_t lds_li
   return launch_repair_back_split(a, ell_k, lds_limit, s, s, nullptr);
 }
 
+namespace {
+
+// one tier's launch: the instantiation for the graph's ELL width, with the
+// drain tests only when the run stages drained nodes
+template <uint32_t kTier>
+hipError_t launch_tier(const RepairArgs& a, uint32_t ell_k, uint32_t grid, uint32_t block, size_t lds,
+                       hipStream_t s, uint32_t cap_a, uint32_t cap_e, uint32_t q) {
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, s, a, cap_a, cap_e, q);
+    return hipGetLastError();
+  };
+  if (a.drn_ptr)
+    return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, true>) : go(whatif_repair_kernel<4, kTier, true>);
+  return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, false>) : go(whatif_repair_kernel<4, kTier, false>);
+}
+
+}  // namespace
+
 hipError_t launch_repair_back_split(const RepairArgs& a, uint32_t ell_k, size_t lds_limit, hipStream_t s,
                                     hipStream_t s3, hipEvent_t mid) {
   if (a.n_req == 0) return hipSuccess;
@@ -428,13 +479,8 @@ hipError_t launch_repair_back_split(const RepairArgs& a, uint32_t ell_k, size_t 
   const size_t lds1 = tier1_lds(a, &sa, &se);
   const size_t lds2 = repair_lds_bytes(a.n_nodes, a.cap_a, a.cap_e);
   if (lds1 < lds2) {
-    if (ell_k == 8)
-      hipLaunchKernelGGL((whatif_repair_kernel<8, kWhatifTierSmall>), dim3(tier_grid(a, lds_limit, lds1, 16)),
-                         dim3(128), lds1, s, a, sa, se, 0u);
-    else
-      hipLaunchKernelGGL((whatif_repair_kernel<4, kWhatifTierSmall>), dim3(tier_grid(a, lds_limit, lds1, 16)),
-                         dim3(128), lds1, s, a, sa, se, 0u);
-    const hipError_t e1 = hipGetLastError();
+    const hipError_t e1 =
+        launch_tier<kWhatifTierSmall>(a, ell_k, tier_grid(a, lds_limit, lds1, 16), 128, lds1, s, sa, se, 0u);
     if (e1 != hipSuccess) return e1;
   }
   // without the small tier, tier 2 drains queue 0 itself
@@ -443,26 +489,16 @@ hipError_t launch_repair_back_split(const RepairArgs& a, uint32_t ell_k, size_t 
   const bool no_t2 = a.skip_large && lds1 < lds2;
   hipError_t e = hipSuccess;
   if (!no_t2) {
-    if (ell_k == 8)
-      hipLaunchKernelGGL((whatif_repair_kernel<8, kWhatifTierLarge>), dim3(tier_grid(a, lds_limit, lds2, 8)),
-                         dim3(256), lds2, s, a, a.cap_a, a.cap_e, q2);
-    else
-      hipLaunchKernelGGL((whatif_repair_kernel<4, kWhatifTierLarge>), dim3(tier_grid(a, lds_limit, lds2, 8)),
-                         dim3(256), lds2, s, a, a.cap_a, a.cap_e, q2);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = launch_tier<kWhatifTierLarge>(a, ell_k, tier_grid(a, lds_limit, lds2, 8), 256, lds2, s, a.cap_a, a.cap_e,
+                                      q2);
+    if (e != hipSuccess) return e;
   }
   if (a.n_slots == 0) return e;
   const uint32_t qs = no_t2 ? q2 : q2 + 1u;
   if (s3 != s) {
     if ((e = hipEventRecord(mid, s)) != hipSuccess || (e = hipStreamWaitEvent(s3, mid, 0)) != hipSuccess) return e;
   }
-  if (ell_k == 8)
-    hipLaunchKernelGGL((whatif_repair_kernel<8, kWhatifTierSlot>), dim3(a.n_slots), dim3(kSlotBlock), 0, s3, a,
-                       a.n_nodes, a.n_recs, qs);
-  else
-    hipLaunchKernelGGL((whatif_repair_kernel<4, kWhatifTierSlot>), dim3(a.n_slots), dim3(kSlotBlock), 0, s3, a,
-                       a.n_nodes, a.n_recs, qs);
-  return hipGetLastError();
+  return launch_tier<kWhatifTierSlot>(a, ell_k, a.n_slots, kSlotBlock, 0, s3, a.n_nodes, a.n_recs, qs);
 }
 
 uint32_t repair_slot_queue(const RepairArgs& a) {

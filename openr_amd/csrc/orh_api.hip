@@ -1596,22 +1596,35 @@ int whatif_stage(orh_whatif* job, size_t words, uint32_t** h, uint32_t** d) {
 // without slots, the full search for what outgrew tier 2 on the job's side
 // streams, over job-owned memory (slots, labels), joined back into the
 // context stream through side_ev
+// drn_ptr / drn_nodes (nullable: none): per request the nodes it drains, i.e.
+// treats as overloaded (orh_whatif_run_drains)
 int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const uint32_t* ign_ptr,
-               const uint32_t* ign_links, uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info) {
+               const uint32_t* ign_links, const uint32_t* drn_ptr, const uint32_t* drn_nodes, uint32_t* d_dist,
+               uint32_t* d_nh, uint32_t* d_info) {
   orh_graph* g = job->g;
   orh_ctx* ctx = g->ctx;
   const uint32_t N = g->n_nodes, m = static_cast<uint32_t>(job->srcs.size());
   for (uint32_t i = 0; i < n_req; ++i)
     if (src_idx[i] >= m) return fail(ctx, ORH_E_INVALID, "orh_whatif_run: source index out of range");
-  // staging: base_row[n] | srcs[n] | ign_ptr[n+1] | ign[..] | cut_ptr[n+1] | (pad to 16 B) cuts uint4[..]
+  // staging: base_row[n] | srcs[n] | ign_ptr[n+1] | ign[..] | with drains: drn_ptr[n+1] | drn[..] |
+  //          cut_ptr[n+1] | (pad to 16 B) cuts uint4[..]
   const uint32_t n_ign = ign_ptr[n_req];
   size_t n_cuts = 0;
   for (uint32_t k = 0; k < n_ign; ++k) {
     const uint32_t l = ign_links[k];
     if (l < g->n_links) n_cuts += (g->link_ent[2 * static_cast<size_t>(l)] != ~0u) + (g->link_ent[2 * static_cast<size_t>(l) + 1] != ~0u);
   }
+  // a drained node's out-records are cuts too (an upper bound here: the sets
+  // are deduplicated, and lose the request's source, while they are staged)
+  const uint32_t n_drn = drn_ptr ? drn_ptr[n_req] : 0u;
+  for (uint32_t k = 0; k < n_drn; ++k) {
+    const uint32_t x = drn_nodes[k];
+    if (x >= N) return fail(ctx, ORH_E_INVALID, "orh_whatif_run_drains: drained node out of range");
+    n_cuts += g->row_ptr[x + 1] - g->row_ptr[x];
+  }
   const size_t off_src = n_req, off_ip = 2 * size_t{n_req}, off_ign = off_ip + n_req + 1;
-  const size_t off_cp = off_ign + n_ign;
+  const size_t off_dp = off_ign + n_ign, off_drn = off_dp + n_req + 1;
+  const size_t off_cp = drn_ptr ? off_drn + n_drn : off_ign + n_ign;
   const size_t off_cuts = (off_cp + n_req + 1 + 3) & ~size_t{3};
   const size_t words = off_cuts + 4 * n_cuts + 4;
   {
@@ -1638,9 +1651,10 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
   uint32_t* hc = h + off_cp;
   uint4* cuts = reinterpret_cast<uint4*>(h + off_cuts);
   const std::vector<uint32_t>& erow = entry_rows(g);
-  size_t ni = 0, nc = 0;
+  size_t ni = 0, nc = 0, nd = 0;
   hp[0] = 0;
   hc[0] = 0;
+  if (drn_ptr) h[off_dp] = 0;
   for (uint32_t i = 0; i < n_req; ++i) {
     uint32_t* set = hi + ni;
     size_t len = 0;
@@ -1658,6 +1672,25 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
     }
     ni += len;
     hp[i + 1] = static_cast<uint32_t>(ni);
+    if (drn_ptr) {
+      // the request's drain set, sorted (bsearch on device), without its own
+      // source (an overloaded source still relaxes, LinkState.cpp:831-838);
+      // one cut per out-record of each node: the seeds test their tightness
+      // and skip a tail that is overloaded already or unreached
+      uint32_t* dset = h + off_drn + nd;
+      size_t dl = 0;
+      for (uint32_t k = drn_ptr[i]; k < drn_ptr[i + 1]; ++k)
+        if (drn_nodes[k] != job->srcs[src_idx[i]]) dset[dl++] = drn_nodes[k];
+      std::sort(dset, dset + dl);
+      dl = static_cast<size_t>(std::unique(dset, dset + dl) - dset);
+      for (size_t k = 0; k < dl; ++k) {
+        const uint32_t x = dset[k];
+        for (uint32_t e = g->row_ptr[x]; e < g->row_ptr[x + 1]; ++e)
+          if (g->meta[e] != ORH_META_EMPTY) cuts[nc++] = make_uint4(x, g->col[e], g->pos[e], 0u);
+      }
+      nd += dl;
+      h[off_dp + i + 1] = static_cast<uint32_t>(nd);
+    }
     hc[i + 1] = static_cast<uint32_t>(nc);
   }
   const int c = job->cur;
@@ -1722,7 +1755,7 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
     if (rc) return rc;
     slot_mem = *p;
   }
-  const size_t nd = static_cast<size_t>(m) * N;
+  const size_t nbase = static_cast<size_t>(m) * N;
   orh::RepairArgs ra{};
   ra.n_nodes = N;
   ra.n_req = n_req;
@@ -1734,11 +1767,15 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
   ra.rev = g->d_rev;
   ra.ovl = g->d_ovl;
   ra.base_dist = job->d_base;
-  ra.base_nh = job->d_base + nd;
+  ra.base_nh = job->d_base + nbase;
   ra.base_row = d;
   ra.srcs = d + off_src;
   ra.ign_ptr = d + off_ip;
   ra.ign = d + off_ign;
+  if (drn_ptr) {
+    ra.drn_ptr = d + off_dp;
+    ra.drn = d + off_drn;
+  }
   ra.cut_ptr = d + off_cp;
   ra.cuts = reinterpret_cast<const uint4*>(d + off_cuts);
   ra.out_dist = d_dist;
@@ -1820,6 +1857,8 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
     a.out_nh = d_nh;
     a.words = 1;
     a.rank_out = g->d_rank_out;
+    a.drain_ptr = ra.drn_ptr;
+    a.drain_nodes = ra.drn;
     a.row_list = ra.queues + static_cast<size_t>(q) * n_req;
     a.row_count = ra.counters + 2 * q;
     e = orh::launch_spf(fp, a, ra.full_cap, job->side);
@@ -1863,6 +1902,8 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
     a.out_nh = d_nh;
     a.words = 1;
     a.rank_out = g->d_rank_out;
+    a.drain_ptr = ra.drn_ptr;
+    a.drain_nodes = ra.drn;
     a.row_mask = flags;
     e = orh::launch_spf(fp, a, n_req, job->side);
     if (e != hipSuccess) return hip_fail(ctx, e, "what-if fallback launch");
@@ -2008,7 +2049,8 @@ int run_repair(orh_graph* g, const orh_spf_request* req, uint32_t* d_dist, uint3
   int rc = whatif_create(g, base_srcs.data(), static_cast<uint32_t>(base_srcs.size()), req->use_link_metric, &job);
   if (rc) return rc;
   ORH_HIP(ctx, hipEventRecord(ctx->evm, ctx->stream));
-  rc = whatif_run(job, n_src, base_row.data(), req->h_ignore_ptr, req->h_ignore_links, d_dist, d_nh, nullptr);
+  rc = whatif_run(job, n_src, base_row.data(), req->h_ignore_ptr, req->h_ignore_links, nullptr, nullptr, d_dist,
+                  d_nh, nullptr);
   if (!rc) rc = whatif_flush(job);
   if (rc) {
     orh_whatif_destroy(job);
@@ -2048,7 +2090,24 @@ int orh_whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, c
   if (job->gen != job->g->gen)
     return fail(ctx, ORH_E_STATE, "orh_whatif_run: the graph changed since the job was created");
   hipSetDevice(ctx->device);
-  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, d_dist, d_nh, d_info);
+  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, nullptr, nullptr, d_dist, d_nh, d_info);
+}
+
+int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
+                          const uint32_t* h_ignore_links, const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
+                          uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info) {
+  if (!job) return ORH_E_INVALID;
+  orh_ctx* ctx = job->g->ctx;
+  join_deferred(ctx);
+  if (n_req == 0) return ORH_OK;
+  if (!h_src_idx || !h_ignore_ptr || (h_ignore_ptr[n_req] && !h_ignore_links) ||
+      (h_drain_ptr && h_drain_ptr[n_req] && !h_drain_nodes) || !d_dist || !d_nh)
+    return fail(ctx, ORH_E_INVALID, "orh_whatif_run_drains: null argument");
+  if (job->gen != job->g->gen)
+    return fail(ctx, ORH_E_STATE, "orh_whatif_run_drains: the graph changed since the job was created");
+  hipSetDevice(ctx->device);
+  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes, d_dist, d_nh,
+                    d_info);
 }
 
 int orh_whatif_refresh(orh_whatif* job) {

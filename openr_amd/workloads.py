@@ -139,6 +139,22 @@ def c4_what_if_job(link_ids: List[int], node_names: List[str], n_links: int = C4
     return srcs, idx, sets
 
 
+def c4_drain_job(node_names: List[str], n_nodes: int = C4_WHATIF_LINKS, n_srcs: int = C4_WHATIF_SRCS,
+                 seed: int = C4_SEED):
+    """The drain analogue of c4_what_if_job: "what if this node is drained?"
+    for n_nodes seeded nodes x n_srcs seeded sources. Returns (sources, per
+    request its source index, per request its (empty) ignore set, per request
+    its drained node names); the requests are in the link job's order, the
+    drained node outermost, one node each."""
+    rng = random.Random(seed + 3)
+    nodes = rng.sample(node_names, min(n_nodes, len(node_names)))
+    srcs = rng.sample(node_names, min(n_srcs, len(node_names)))
+    idx = [i for _ in nodes for i in range(len(srcs))]
+    ignore = [[] for _ in nodes for _ in srcs]
+    drain = [[x] for x in nodes for _ in srcs]
+    return srcs, idx, ignore, drain
+
+
 def c4_ksp2_pairs(node_names: List[str], n_pairs: int, seed: int = C4_SEED):
     rng = random.Random(seed + 2)
     out = []
