@@ -392,6 +392,60 @@ int orh_whatif_refresh(orh_whatif* job);
  * orh_whatif_flush every row of every run so far is complete in stream order
  * (a later run waits by itself before it overwrites rows of an earlier one). */
 int orh_whatif_flush(orh_whatif* job);
+/* Impact summaries: what a request's failure or drain does to its source's
+ * routes, reduced on the device while the request's row is still in its
+ * buffer (a job's rows are far too many to copy out: C4 is 105 GB).
+ * Request i's row (d_dist + i*N, d_nh + i*N, one mask word per node: the rows
+ * an orh_whatif_run / _run_drains of this job wrote) is compared with the
+ * job's base row of source h_src_idx[i] (orh_whatif_base_rows), node by node.
+ * A node unreached in the base row is in no class, and neither is the
+ * request's source. */
+typedef struct orh_whatif_impact_rec { /* 48 bytes, 8-byte aligned */
+  uint32_t lost;         /* reached in the base row, unreached in the request's row */
+  uint32_t farther;      /* reached in both, distance differs (it can only grow) */
+  uint32_t rehomed;      /* reached in both, same distance, first-hop mask differs */
+  uint32_t narrowed;     /* reached in both, popcount(mask) smaller than in the base row
+                            (counted whether or not the distance changed) */
+  uint32_t max_stretch;  /* max over `farther` of dist_req - dist_base, 0 if none */
+  uint32_t worst_node;   /* the node with that stretch, the smallest id on a tie;
+                            ORH_NO_NODE (0xFFFFFFFF) if farther == 0 */
+  uint64_t sum_stretch;  /* sum over `farther` of dist_req - dist_base */
+  uint64_t lost_weight;  /* sum of weight[v] over `lost` (0 without weights) */
+  uint64_t moved_weight; /* sum of weight[v] over lost + farther + rehomed */
+} orh_whatif_impact_rec;
+typedef struct orh_whatif_impact_opts { /* zero-initialise; every field nullable */
+  const uint32_t* d_weight; /* [N] per-node weight, e.g. prefixes the node advertises */
+  uint32_t* d_node_lost;    /* [N] += 1 per request in which the node is lost */
+  uint32_t* d_node_moved;   /* [N] += 1 per request in which it is lost, farther or rehomed */
+} orh_whatif_impact_opts;
+/* d_out [n_req] records (device). opts nullable (no weights, no node arrays).
+ * - Ordering: asynchronous on the context stream. The call first makes the
+ *   context stream wait for every pending run of this job whose output span
+ *   overlaps the given rows (the test a run applies before it overwrites rows;
+ *   not a full orh_whatif_flush); a later run into the same buffers is ordered
+ *   behind it by the context stream.
+ * - d_info (nullable): the d_info of the run that wrote the rows. Where
+ *   ORH_WHATIF_TIER(d_info[i]) == 0 the source's row stands: the record is all
+ *   zeros with worst_node = ORH_NO_NODE and the request's row is NOT read
+ *   (under ORH_WHATIF_SHARE_BASE it was never written). With d_info == NULL
+ *   every row is scanned; NULL on a SHARE_BASE job is ORH_E_INVALID.
+ * - A graph so large that a run has no tier-3 slots (one slot's state exceeds
+ *   the slot budget: tens of millions of records) leaves tier 0 in d_info for
+ *   the requests its full search re-derived, so there d_info is ignored and
+ *   every row is scanned; on a SHARE_BASE job that is ORH_E_UNSUPPORTED.
+ * - Validation, before anything is queued: h_src_idx[i] >= the job's source
+ *   count, or a NULL job, rows or d_out with n_req > 0: ORH_E_INVALID; a graph
+ *   structure changed since the job was created: ORH_E_STATE; n_req == 0:
+ *   ORH_OK.
+ * - d_node_lost / d_node_moved accumulate: the caller zeroes them, and the
+ *   chunks of one job add up.
+ * - After orh_whatif_refresh the rows of earlier runs no longer belong to the
+ *   base rows; summarising them against the new base rows is the caller's
+ *   business.
+ * - h_src_idx may be reused once the call returns. */
+int orh_whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* d_dist,
+                      const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_impact_opts* opts,
+                      orh_whatif_impact_rec* d_out);
 /* device time from the job's creation (base searches) to the end of its last
  * run (flushes; HIP events; waits for that run) */
 int orh_whatif_elapsed_ms(orh_whatif* job, double* ms_out);

@@ -634,6 +634,60 @@ struct RibStatementProbe {  // a lone RibPolicyStatement (RibPolicyTest.cpp stat
   RibPolicyStatement st;
 };
 
+// what-if impact (WhatIfBatch / MultiDeviceWhatIf): weights as a dict
+// {node name: weight} or an iterable of (node name, weight) pairs, or None
+std::vector<std::pair<std::string, uint32_t>> weightPairs(const py::object& w) {
+  std::vector<std::pair<std::string, uint32_t>> out;
+  if (w.is_none()) return out;
+  if (py::isinstance<py::dict>(w)) {
+    for (auto item : w.cast<py::dict>()) out.emplace_back(str(item.first), item.second.cast<uint32_t>());
+    return out;
+  }
+  for (auto item : w) {
+    auto t = item.cast<py::tuple>();
+    if (t.size() != 2) throw std::invalid_argument("set_impact: weights are (node name, weight) pairs");
+    out.emplace_back(str(t[0]), t[1].cast<uint32_t>());
+  }
+  return out;
+}
+
+// the records as a dict of arrays keyed by orh_whatif_impact_rec's field names
+template <class Job>
+py::dict impactDict(const Job& b, size_t n) {
+  std::vector<orh_whatif_impact_rec> rec(n);
+  b.impact(rec.data());
+  py::dict d;
+  auto col32 = [&](const char* name, uint32_t orh_whatif_impact_rec::*f) {
+    py::array_t<uint32_t> a(n);
+    for (size_t i = 0; i < n; ++i) a.mutable_data()[i] = rec[i].*f;
+    d[name] = a;
+  };
+  auto col64 = [&](const char* name, uint64_t orh_whatif_impact_rec::*f) {
+    py::array_t<uint64_t> a(n);
+    for (size_t i = 0; i < n; ++i) a.mutable_data()[i] = rec[i].*f;
+    d[name] = a;
+  };
+  col32("lost", &orh_whatif_impact_rec::lost);
+  col32("farther", &orh_whatif_impact_rec::farther);
+  col32("rehomed", &orh_whatif_impact_rec::rehomed);
+  col32("narrowed", &orh_whatif_impact_rec::narrowed);
+  col32("max_stretch", &orh_whatif_impact_rec::max_stretch);
+  col32("worst_node", &orh_whatif_impact_rec::worst_node);
+  col64("sum_stretch", &orh_whatif_impact_rec::sum_stretch);
+  col64("lost_weight", &orh_whatif_impact_rec::lost_weight);
+  col64("moved_weight", &orh_whatif_impact_rec::moved_weight);
+  return d;
+}
+
+template <class Job>
+py::tuple nodeImpactArrays(const Job& b, size_t n) {
+  py::array_t<uint32_t> lost(n), moved(n);
+  std::fill_n(lost.mutable_data(), n, 0u);
+  std::fill_n(moved.mutable_data(), n, 0u);
+  b.nodeImpact(lost.mutable_data(), moved.mutable_data());
+  return py::make_tuple(lost, moved);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_openr_host, m) {
@@ -1118,6 +1172,13 @@ PYBIND11_MODULE(_openr_host, m) {
              b.fetch(i, dist.mutable_data(), nh.mutable_data());
              return py::make_tuple(dist, nh);
            })
+      .def("set_impact",
+           [](WhatIfBatch& b, bool on, const py::object& weights, bool nodeCounts) {
+             b.setImpact(on, weightPairs(weights), nodeCounts);
+           },
+           py::arg("on") = true, py::arg("weights") = py::none(), py::arg("node_counts") = false)
+      .def("impact", [](const WhatIfBatch& b) { return impactDict(b, b.requests()); })
+      .def("node_impact", [](const WhatIfBatch& b) { return nodeImpactArrays(b, b.nodes()); })
       .def_property_readonly("requests", &WhatIfBatch::requests)
       .def_property_readonly("chunk", &WhatIfBatch::chunk)
       .def_property_readonly("nodes", &WhatIfBatch::nodes)
@@ -1141,11 +1202,19 @@ PYBIND11_MODULE(_openr_host, m) {
              b.info(out.mutable_data());
              return out;
            })
-      .def("digests", [](const MultiDeviceWhatIf& b) {
-        py::array_t<uint64_t> out(b.requests());
-        b.digests(out.mutable_data());
-        return out;
-      });
+      .def("digests",
+           [](const MultiDeviceWhatIf& b) {
+             py::array_t<uint64_t> out(b.requests());
+             b.digests(out.mutable_data());
+             return out;
+           })
+      .def("set_impact",
+           [](MultiDeviceWhatIf& b, bool on, const py::object& weights, bool nodeCounts) {
+             b.setImpact(on, weightPairs(weights), nodeCounts);
+           },
+           py::arg("on") = true, py::arg("weights") = py::none(), py::arg("node_counts") = false)
+      .def("impact", [](const MultiDeviceWhatIf& b) { return impactDict(b, b.requests()); })
+      .def("node_impact", [](const MultiDeviceWhatIf& b) { return nodeImpactArrays(b, b.nodes()); });
   py::class_<MultiDeviceKthPaths>(m, "MultiDeviceKthPaths")
       .def("run", &MultiDeviceKthPaths::run, py::call_guard<py::gil_scoped_release>())
       .def("run_block", &MultiDeviceKthPaths::runBlock, py::arg("block"))

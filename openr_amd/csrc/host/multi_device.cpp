@@ -343,6 +343,39 @@ void MultiDeviceWhatIf::digests(uint64_t* out) const {
   }
 }
 
+void MultiDeviceWhatIf::setImpact(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights,
+                                  bool nodeCounts) {
+  for (auto& b : blocks_)
+    if (b.job) b.job->setImpact(on, weights, nodeCounts);
+}
+
+void MultiDeviceWhatIf::impact(orh_whatif_impact_rec* out) const {
+  std::vector<orh_whatif_impact_rec> tmp;
+  for (const auto& b : blocks_) {
+    if (!b.job) continue;
+    tmp.resize(b.reqs.size());
+    b.job->impact(tmp.data());
+    for (size_t k = 0; k < b.reqs.size(); ++k) out[b.reqs[k]] = tmp[k];
+  }
+}
+
+void MultiDeviceWhatIf::nodeImpact(uint32_t* lost, uint32_t* moved) const {
+  std::vector<uint32_t> l, m;
+  bool first = true;
+  for (const auto& b : blocks_) {
+    if (!b.job) continue;
+    const size_t n = b.job->nodes();
+    l.resize(n);
+    m.resize(n);
+    b.job->nodeImpact(l.data(), m.data());
+    for (size_t v = 0; v < n; ++v) {
+      lost[v] = (first ? 0u : lost[v]) + l[v];
+      moved[v] = (first ? 0u : moved[v]) + m[v];
+    }
+    first = false;
+  }
+}
+
 // ---- MultiDeviceKthPaths -----------------------------------------------------
 MultiDeviceKthPaths::MultiDeviceKthPaths(const ReplicatedLinkState& rls,
                                          const std::vector<std::pair<std::string, std::string>>& pairs)

@@ -128,6 +128,11 @@ class MultiDeviceWhatIf {
   std::pair<size_t, size_t> sourceBlock(size_t r) const { return {blocks_.at(r).lo, blocks_.at(r).hi}; }
   size_t blockRequests(size_t r) const { return blocks_.at(r).reqs.size(); }
   size_t requests() const { return total_; }
+  uint32_t nodes() const {  // the graph's node count (0 for a job without requests)
+    for (const auto& b : blocks_)
+      if (b.job) return b.job->nodes();
+    return 0;
+  }
   // device ms of block r's last run; 0 for a block with no requests (no job)
   // or one released since
   double lastMs(size_t r) const {
@@ -136,6 +141,12 @@ class MultiDeviceWhatIf {
   }
   void info(uint32_t* out) const;     // [requests()] in the caller's order
   void digests(uint64_t* out) const;  // [requests()] (setDigests(true) before the run)
+  // impact summaries (WhatIfBatch::setImpact) on every block: records in the
+  // caller's request order; the node counters are summed over the blocks
+  void setImpact(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights = {},
+                 bool nodeCounts = false);
+  void impact(orh_whatif_impact_rec* out) const;            // [requests()]
+  void nodeImpact(uint32_t* lost, uint32_t* moved) const;  // [nodes] each
 
  private:
   struct Block {

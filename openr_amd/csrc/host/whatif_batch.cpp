@@ -86,7 +86,26 @@ void WhatIfBatch::allocate() {
   }
 }
 
+void WhatIfBatch::freeImpact() {
+  if (dImpact_) orh_device_free(ctx_, dImpact_);
+  if (dWeight_) orh_device_free(ctx_, dWeight_);
+  if (dNodeLost_) orh_device_free(ctx_, dNodeLost_);
+  if (dNodeMoved_) orh_device_free(ctx_, dNodeMoved_);
+  dImpact_ = nullptr;
+  dWeight_ = dNodeLost_ = dNodeMoved_ = nullptr;
+}
+
 void WhatIfBatch::release() {
+  if (impactRan_ && dImpact_) {  // the last run's summaries outlive the buffers
+    hImpact_.resize(srcIdx_.size());
+    impact(hImpact_.data());
+    if (nodeCounts_ && dNodeLost_) {
+      hNodeLost_.resize(n_);
+      hNodeMoved_.resize(n_);
+      nodeImpact(hNodeLost_.data(), hNodeMoved_.data());
+    }
+  }
+  freeImpact();
   if (job_) {
     orh_whatif_destroy(job_);
     job_ = nullptr;
@@ -100,6 +119,7 @@ void WhatIfBatch::release() {
 }
 
 WhatIfBatch::~WhatIfBatch() {
+  impactRan_ = false;  // nothing to keep
   release();
   if (dInfo_) orh_device_free(ctx_, dInfo_);
   if (dDigest_) orh_device_free(ctx_, dDigest_);
@@ -115,7 +135,81 @@ void WhatIfBatch::setDigests(bool on) {
         "orh_device_alloc");
 }
 
+void WhatIfBatch::setImpact(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights,
+                            bool nodeCounts) {
+  std::vector<uint32_t> w;
+  if (on && !weights.empty()) {
+    w.assign(n_, 0u);
+    for (const auto& [name, x] : weights) {
+      auto id = ls_.nodeId(name);
+      if (!id || *id >= n_) throw std::invalid_argument("WhatIfBatch: unknown weighted node " + name);
+      w[*id] = x;
+    }
+  }
+  impact_ = on;
+  nodeCounts_ = on && nodeCounts;
+  weights_ = std::move(w);
+  if (dWeight_) {  // the next run uploads the new ones
+    orh_device_free(ctx_, dWeight_);
+    dWeight_ = nullptr;
+  }
+}
+
+// chunk c's rows, still in buffer c % nBuf_, into its requests' records
+void WhatIfBatch::queueImpact(size_t c) {
+  const Chunk& ch = chunks_[c];
+  const int b = static_cast<int>(c % nBuf_);
+  orh_whatif_impact_opts opts{};
+  opts.d_weight = weights_.empty() ? nullptr : dWeight_;
+  opts.d_node_lost = nodeCounts_ ? dNodeLost_ : nullptr;
+  opts.d_node_moved = nodeCounts_ ? dNodeMoved_ : nullptr;
+  check(ctx_,
+        orh_whatif_impact(job_, static_cast<uint32_t>(ch.hi - ch.lo), srcIdx_.data() + ch.lo, dDist_[b], dNh_[b],
+                          dInfo_ + ch.lo, &opts, dImpact_ + ch.lo),
+        "orh_whatif_impact");
+}
+
+void WhatIfBatch::impact(orh_whatif_impact_rec* out) const {
+  if (!impactRan_) throw std::logic_error("WhatIfBatch: impact was not enabled for the last run");
+  if (dImpact_)
+    check(ctx_, orh_memcpy_d2h(ctx_, out, dImpact_, srcIdx_.size() * sizeof(orh_whatif_impact_rec)),
+          "orh_memcpy_d2h");
+  else
+    std::copy(hImpact_.begin(), hImpact_.end(), out);
+}
+
+void WhatIfBatch::nodeImpact(uint32_t* lost, uint32_t* moved) const {
+  if (!impactRan_ || !nodeCounts_)
+    throw std::logic_error("WhatIfBatch: node counts were not enabled for the last run");
+  if (dNodeLost_) {
+    check(ctx_, orh_memcpy_d2h(ctx_, lost, dNodeLost_, n_ * 4ull), "orh_memcpy_d2h");
+    check(ctx_, orh_memcpy_d2h(ctx_, moved, dNodeMoved_, n_ * 4ull), "orh_memcpy_d2h");
+  } else {
+    std::copy(hNodeLost_.begin(), hNodeLost_.end(), lost);
+    std::copy(hNodeMoved_.begin(), hNodeMoved_.end(), moved);
+  }
+}
+
 void WhatIfBatch::run() {
+  impactRan_ = false;
+  if (impact_) {  // buffers of the mode; the node counters start at zero (before the job's clock)
+    auto alloc = [&](auto** p, size_t bytes) {
+      if (!*p) check(ctx_, orh_device_alloc(ctx_, std::max<size_t>(bytes, 8), reinterpret_cast<void**>(p)),
+                     "orh_device_alloc");
+    };
+    alloc(&dImpact_, srcIdx_.size() * sizeof(orh_whatif_impact_rec));
+    if (!weights_.empty() && !dWeight_) {
+      alloc(&dWeight_, n_ * 4ull);
+      check(ctx_, orh_memcpy_h2d(ctx_, dWeight_, weights_.data(), n_ * 4ull), "orh_memcpy_h2d");
+    }
+    if (nodeCounts_) {
+      alloc(&dNodeLost_, n_ * 4ull);
+      alloc(&dNodeMoved_, n_ * 4ull);
+      const std::vector<uint32_t> zero(n_, 0u);
+      check(ctx_, orh_memcpy_h2d(ctx_, dNodeLost_, zero.data(), n_ * 4ull), "orh_memcpy_h2d");
+      check(ctx_, orh_memcpy_h2d(ctx_, dNodeMoved_, zero.data(), n_ * 4ull), "orh_memcpy_h2d");
+    }
+  }
   // the graph as it is now: a what-if job is bound to its graph's structure
   // (orh_whatif_run fails with ORH_E_STATE after a delta or reload)
   {
@@ -151,6 +245,9 @@ void WhatIfBatch::run() {
     const Chunk& ch = chunks_[c];
     const uint32_t nr = static_cast<uint32_t>(ch.hi - ch.lo);
     const int b = static_cast<int>(c % nBuf_);  // cycle the row buffers
+    // this run overwrites the rows of chunk c - nBuf_, and waits for them by
+    // itself: their summary goes right before it
+    if (impact_ && c >= static_cast<size_t>(nBuf_)) queueImpact(c - nBuf_);
     if (drains_)
       check(ctx_,
             orh_whatif_run_drains(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(),
@@ -165,6 +262,11 @@ void WhatIfBatch::run() {
       check(ctx_, orh_whatif_flush(job_), "orh_whatif_flush");
       check(ctx_, orh_row_digest(ctx_, dDist_[b], dNh_[b], 1, n_, nr, dDigest_ + ch.lo), "orh_row_digest");
     }
+  }
+  if (impact_) {  // the chunks still in the buffers
+    const size_t nc = chunks_.size();
+    for (size_t c = nc > static_cast<size_t>(nBuf_) ? nc - nBuf_ : 0; c < nc; ++c) queueImpact(c);
+    impactRan_ = true;
   }
   check(ctx_, orh_whatif_flush(job_), "orh_whatif_flush");
 }

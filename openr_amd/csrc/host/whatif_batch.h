@@ -51,6 +51,21 @@ class WhatIfBatch {
   // digest; each chunk is flushed first, so runs in this mode are slower
   void setDigests(bool on);
   void digests(uint64_t* out) const;
+  // impact mode: every chunk's rows are summarised on the device
+  // (orh_whatif_impact: lost / farther / rehomed / narrowed nodes, stretch,
+  // weights) while they are still in their buffer. A chunk's summary is queued
+  // where the pipeline waits for the chunk anyway - before the run that
+  // reuses its row buffer, or before the final flush - so the mode adds one
+  // streaming pass over the repaired rows and no stall. weights: (node name,
+  // weight) pairs, absent nodes weigh 0, an unknown name is
+  // std::invalid_argument; nodeCounts: per node, in how many requests it is
+  // lost / moved (nodeImpact)
+  void setImpact(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights = {},
+                 bool nodeCounts = false);
+  // [requests()] records of the last run, in the caller's request order
+  void impact(orh_whatif_impact_rec* out) const;
+  // [nodes()] each (graph node ids), summed over the last run's requests
+  void nodeImpact(uint32_t* lost, uint32_t* moved) const;
   // rows of request i; only the last chunk's rows are still in the buffers
   // (std::out_of_range otherwise)
   void fetch(size_t i, uint32_t* dist, uint32_t* nh) const;
@@ -94,6 +109,20 @@ class WhatIfBatch {
   uint32_t* dInfo_{nullptr};
   uint64_t* dDigest_{nullptr};      // [requests] (verification mode)
   uint64_t* dBaseDigest_{nullptr};  // [sources]
+  // impact mode
+  void queueImpact(size_t c);
+  void freeImpact();
+  bool impact_{false};
+  bool nodeCounts_{false};
+  bool impactRan_{false};  // the last run filled dImpact_ (and the node arrays)
+  std::vector<uint32_t> weights_;            // [n_] (empty: none)
+  orh_whatif_impact_rec* dImpact_{nullptr};  // [requests]
+  uint32_t* dWeight_{nullptr};               // [n_]
+  uint32_t* dNodeLost_{nullptr};             // [n_]
+  uint32_t* dNodeMoved_{nullptr};            // [n_]
+  // the last run's results, kept on the host when release() frees the above
+  std::vector<orh_whatif_impact_rec> hImpact_;
+  std::vector<uint32_t> hNodeLost_, hNodeMoved_;
 };
 
 }  // namespace openr_amd

@@ -1,9 +1,12 @@
-// Internal interface of the what-if repair kernels (whatif_kernels.hip).
+// Internal interface of the what-if repair kernels (whatif_kernels.hip) and
+// the impact summaries over their rows (whatif_impact_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+struct orh_whatif_impact_rec;  // include/openr_hip.h
 
 namespace orh {
 
@@ -103,5 +106,26 @@ hipError_t launch_repair_back_split(const RepairArgs& a, uint32_t ell_k, size_t 
 // (row_digest_kernel), into out[r]
 hipError_t launch_row_digest(const uint32_t* dist, const uint32_t* nh, uint32_t words, uint32_t n,
                              uint32_t rows, uint64_t* out, hipStream_t s);
+
+// ---- what-if impact (whatif_impact_kernels.hip) ---------------------------
+// request r's row (dist / nh + r * N) against base row base_row[r], reduced to
+// out[r] (orh_whatif_impact in include/openr_hip.h has the classes)
+struct ImpactArgs {
+  uint32_t n_nodes;
+  uint32_t n_req;
+  const uint32_t* base_dist;  // [m][N]
+  const uint32_t* base_nh;    // [m][N], one mask word
+  const uint32_t* base_row;   // [n_req] base row of the request's source
+  const uint32_t* srcs;       // [n_req] its source node (in no class)
+  const uint32_t* dist;       // [n_req][N]
+  const uint32_t* nh;         // [n_req][N]
+  const uint32_t* info;       // [n_req] (nullable: every row is scanned); tier 0: the row is not read
+  const uint32_t* weight;     // [N] (nullable)
+  uint32_t* node_lost;        // [N] (nullable), accumulated
+  uint32_t* node_moved;       // [N] (nullable), accumulated
+  ::orh_whatif_impact_rec* out;  // [n_req]
+};
+// zeroes the records, scans, then finishes max_stretch / worst_node
+hipError_t launch_whatif_impact(const ImpactArgs& a, hipStream_t s);
 
 }  // namespace orh

@@ -1566,6 +1566,14 @@ struct orh_whatif {
   hipEvent_t mid_ev[kRunSlots] = {};
   uint8_t* t3_slots[kRunSlots] = {};
   size_t t3_slots_cap[kRunSlots] = {};
+  // orh_whatif_impact's request staging (base row | source node per request),
+  // cycled like the run slots' but its own: an impact call is queued between
+  // runs whose staging is still in flight
+  uint32_t* h_imp[kRunSlots] = {};
+  uint32_t* d_imp[kRunSlots] = {};
+  size_t imp_cap[kRunSlots] = {};     // u32, both sides
+  hipEvent_t imp_ev[kRunSlots] = {};  // upload done, and the kernels that read it
+  int imp_cur = 0;
 };
 
 namespace {
@@ -1935,6 +1943,80 @@ int whatif_flush(orh_whatif* job) {
   return ORH_OK;
 }
 
+// orh_whatif_impact: the requests' rows against their sources' base rows,
+// one record each, on the context stream behind the runs that wrote the rows
+int whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const uint32_t* d_dist,
+                  const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_impact_opts* opts,
+                  orh_whatif_impact_rec* d_out) {
+  orh_graph* g = job->g;
+  orh_ctx* ctx = g->ctx;
+  const uint32_t N = g->n_nodes, m = static_cast<uint32_t>(job->srcs.size());
+  for (uint32_t i = 0; i < n_req; ++i)
+    if (src_idx[i] >= m) return fail(ctx, ORH_E_INVALID, "orh_whatif_impact: source index out of range");
+  const bool share = (job->flags & ORH_WHATIF_SHARE_BASE) != 0;
+  if (share && !d_info)
+    return fail(ctx, ORH_E_INVALID, "orh_whatif_impact: a SHARE_BASE job's tier-0 rows were never written, d_info is needed");
+  // a graph whose runs have no tier-3 slots (whatif_run's n_slots == 0) leaves
+  // tier 0 in d_info for the requests its full search re-derived: tier 0 does
+  // not prove there that the row stands, so every row is scanned
+  if (kRepairSlotBudget / std::max<size_t>(orh::repair_slot_bytes(N, g->n_recs), 1) == 0) {
+    if (share) return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_impact: SHARE_BASE on a graph without repair slots");
+    d_info = nullptr;
+  }
+  // every pending run whose rows overlap the given ones joins the context stream
+  {
+    const uintptr_t lo = std::min(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh));
+    const uintptr_t hi = std::max(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh)) +
+                         size_t{n_req} * N * 4;
+    for (int k = 0; k < kRunSlots; ++k)
+      if (job->pending[k] && lo < job->out_hi[k] && job->out_lo[k] < hi) {
+        ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, job->side_ev[k], 0));
+        job->pending[k] = false;
+      }
+  }
+  const int c = job->imp_cur;
+  const size_t words = 2 * size_t{n_req};
+  if (job->imp_ev[c]) ORH_HIP(ctx, hipEventSynchronize(job->imp_ev[c]));  // its last upload is done
+  if (words > job->imp_cap[c]) {
+    if (job->h_imp[c]) hipHostFree(job->h_imp[c]);
+    hipFree(job->d_imp[c]);
+    job->h_imp[c] = nullptr;
+    job->d_imp[c] = nullptr;
+    job->imp_cap[c] = 0;
+    const size_t cap = std::max<size_t>(words + words / 4, 4096);
+    ORH_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&job->h_imp[c]), cap * 4, hipHostMallocDefault));
+    ORH_HIP(ctx, hipMalloc(&job->d_imp[c], cap * 4));
+    job->imp_cap[c] = cap;
+  }
+  if (!job->imp_ev[c]) ORH_HIP(ctx, hipEventCreateWithFlags(&job->imp_ev[c], hipEventDisableTiming));
+  uint32_t* h = job->h_imp[c];
+  uint32_t* d = job->d_imp[c];
+  std::memcpy(h, src_idx, n_req * 4ull);
+  for (uint32_t i = 0; i < n_req; ++i) h[n_req + i] = job->srcs[src_idx[i]];
+  job->imp_cur = (c + 1) % kRunSlots;
+  ORH_HIP(ctx, hipMemcpyAsync(d, h, words * 4, hipMemcpyHostToDevice, ctx->stream));
+  ORH_HIP(ctx, hipEventRecord(job->imp_ev[c], ctx->stream));
+  orh::ImpactArgs a{};
+  a.n_nodes = N;
+  a.n_req = n_req;
+  a.base_dist = job->d_base;
+  a.base_nh = job->d_base + static_cast<size_t>(m) * N;
+  a.base_row = d;
+  a.srcs = d + n_req;
+  a.dist = d_dist;
+  a.nh = d_nh;
+  a.info = d_info;
+  if (opts) {
+    a.weight = opts->d_weight;
+    a.node_lost = opts->d_node_lost;
+    a.node_moved = opts->d_node_moved;
+  }
+  a.out = d_out;
+  const hipError_t e = orh::launch_whatif_impact(a, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "what-if impact launch");
+  return ORH_OK;
+}
+
 // the plain SPFs of the job's sources into its base rows, on the graph as it
 // is now (create, and orh_whatif_refresh after topology changes); the side
 // parts of earlier runs, which read the old rows, are joined first
@@ -2110,6 +2192,20 @@ int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src
                     d_info);
 }
 
+int orh_whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* d_dist,
+                      const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_impact_opts* opts,
+                      orh_whatif_impact_rec* d_out) {
+  if (!job) return ORH_E_INVALID;
+  orh_ctx* ctx = job->g->ctx;
+  join_deferred(ctx);
+  if (n_req == 0) return ORH_OK;
+  if (!h_src_idx || !d_dist || !d_nh || !d_out) return fail(ctx, ORH_E_INVALID, "orh_whatif_impact: null argument");
+  if (job->gen != job->g->gen)
+    return fail(ctx, ORH_E_STATE, "orh_whatif_impact: the graph changed since the job was created");
+  hipSetDevice(ctx->device);
+  return whatif_impact(job, n_req, h_src_idx, d_dist, d_nh, d_info, opts, d_out);
+}
+
 int orh_whatif_refresh(orh_whatif* job) {
   if (!job) return ORH_E_INVALID;
   hipSetDevice(job->g->ctx->device);
@@ -2174,6 +2270,12 @@ int orh_whatif_destroy(orh_whatif* job) {
     }
     if (job->h_stage[c]) hipHostFree(job->h_stage[c]);
     hipFree(job->d_stage[c]);
+    if (job->imp_ev[c]) {
+      hipEventSynchronize(job->imp_ev[c]);
+      hipEventDestroy(job->imp_ev[c]);
+    }
+    if (job->h_imp[c]) hipHostFree(job->h_imp[c]);
+    hipFree(job->d_imp[c]);
   }
   hipFree(job->d_base);
   hipFree(job->own_slots);

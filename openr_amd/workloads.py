@@ -155,6 +155,14 @@ def c4_drain_job(node_names: List[str], n_nodes: int = C4_WHATIF_LINKS, n_srcs: 
     return srcs, idx, ignore, drain
 
 
+def c4_node_weights(node_names: List[str], seed: int = C4_SEED, max_prefixes: int = 64):
+    """Seeded per-node weights for what-if impact summaries on the C4 WAN: the
+    prefixes each node advertises, uniform in [0, max_prefixes], as
+    {node name: weight}."""
+    rng = random.Random(seed + 4)
+    return {x: rng.randint(0, max_prefixes) for x in node_names}
+
+
 def c4_ksp2_pairs(node_names: List[str], n_pairs: int, seed: int = C4_SEED):
     rng = random.Random(seed + 2)
     out = []
