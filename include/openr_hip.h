@@ -322,7 +322,7 @@ int orh_spf_batch_exact(orh_graph* g, const orh_spf_request* req, uint32_t words
 #define ORH_GRAPH_WIDE_METRIC 2u /* link-metric path sums can reach 2^32 - 1 */
 int orh_graph_flags(const orh_graph* g, uint32_t* flags);
 
-/* ---- what-if jobs (batched link-failure and node-drain SPFs) ------------
+/* ---- what-if jobs (batched link-failure, node-drain and cost-out SPFs) ---
  * runSpf(src, useLinkMetric, linksToIgnore) (LinkState.cpp:808-882) for many
  * (source, ignore set) requests over a fixed source set - the C4 shape,
  * "4,096 links x 64 sources" (SURVEY.md §8d). orh_whatif_create searches the
@@ -335,6 +335,9 @@ int orh_graph_flags(const orh_graph* g, uint32_t* flags);
  * reachable but carry no transit traffic (:831-838). A drain removes only the
  * relaxations out of the node, so the same repair covers it: the rows change
  * only below the node's tight out-links, and are as exact.
+ * orh_whatif_run_metrics adds, per request, a set of metric raises (a link
+ * costed out from one end or both, Link::setMetricFromNode, :640-710): the
+ * rows change only below a raised record that was tight, and are as exact.
  * A job is bound to the graph structure it was created on
  * (ORH_E_STATE after a delta or reload). Everything is asynchronous on the
  * context stream; one mask word per node (every source has <= 32 distinct
@@ -361,6 +364,56 @@ int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src
                           const uint32_t* h_ignore_ptr, const uint32_t* h_ignore_links,
                           const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
                           uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info);
+/* orh_whatif_run_drains with, per request, a set of metric raises: costing a
+ * link out (a soft drain). Raise k of request i, h_metrics[h_metric_ptr[i] ..
+ * h_metric_ptr[i+1]), replaces what Link::getMetricFromNode(from_node)
+ * returns for that link (Link::setMetricFromNode, LinkState.cpp:640-710), and
+ * the request's row is runSpf(src_i, use_link_metric, ignore_i) on the graph
+ * with those metrics replaced and the drained nodes overloaded, bit-identical
+ * in distances and first-hop masks. h_metric_ptr == NULL: exactly
+ * orh_whatif_run_drains.
+ * - Raises only. A raise weakens relaxations like an ignored link (a metric
+ *   raised to infinity), so the same repair covers it: the rows change only
+ *   below a raised record that is tight under its old metric, and the
+ *   re-derivation weighs a raised record with its new metric. A lower metric
+ *   shortens paths, which the repair cannot do: that stays a topology change
+ *   (orh_graph_patch_edges + orh_whatif_refresh) and is rejected here.
+ * - A link both ignored and raised in one request is ignored. Of several
+ *   raises of one (link, end) in a request the largest holds.
+ * - A hop-count job (use_link_metric == 0) ignores metrics: its raises are
+ *   validated and then do nothing (tier 0 unless the request changes
+ *   something else).
+ * - Validation, all before anything is queued, per raise in this order: a
+ *   link id >= n_links or a free link slot is skipped, as in ignore sets;
+ *   from_node that is neither ORH_NO_NODE nor an end of the link:
+ *   ORH_E_INVALID; a link that is down: no-op; metric below the current
+ *   w_out of a direction it names: ORH_E_INVALID; equal to it: that direction
+ *   is dropped. With ORH_NO_NODE on asymmetric metrics the value must be >=
+ *   both directions'. The job's distance bound (the one its search plan is
+ *   made for) plus the sum of one request's raises (new - old, per direction)
+ *   >= 2^32 - 1: ORH_E_UNSUPPORTED, because rows are u32. NULL job:
+ *   ORH_E_INVALID without touching a device.
+ * - The full search (tier 4) knows no raised weights: its bucket widths are
+ *   planned from the graph's metric range. A run in which at least one raise
+ *   takes effect therefore runs no full search: ORH_WHATIF_SEARCH_LARGE and
+ *   ORH_WHATIF_FULL are ignored for that run and the global-slot tier, whose
+ *   state is sized for the whole graph and cannot overflow, takes those
+ *   requests; d_info reports tiers 0-3 only. On a graph without tier-3 slots
+ *   (one slot's state exceeds the slot budget: tens of millions of records)
+ *   such a run is ORH_E_UNSUPPORTED; no test can reach that size.
+ * - Ordering, orh_whatif_flush, ORH_WHATIF_SHARE_BASE and orh_whatif_impact
+ *   work as for any other run; a raise only lengthens paths, so impact's
+ *   "distance can only grow" holds. */
+typedef struct orh_whatif_metric {
+  uint32_t link;      /* orh_csr link id */
+  uint32_t from_node; /* the end whose Link::getMetricFromNode changes; ORH_NO_NODE: both ends */
+  uint32_t metric;    /* new value, >= the current one */
+} orh_whatif_metric;
+int orh_whatif_run_metrics(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx,
+                           const uint32_t* h_ignore_ptr, const uint32_t* h_ignore_links,
+                           const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
+                           const uint32_t* h_metric_ptr, const orh_whatif_metric* h_metrics,
+                           uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info);
 #define ORH_WHATIF_TIER(x) ((x) & 7u) /* 0 source row, 1/2 LDS repair, 3 global-slot repair, 4 full search
                                          (subtrees too large for LDS, up to ORH_WHATIF_FULL per run; every
                                          such request without slots) */
@@ -396,7 +449,7 @@ int orh_whatif_flush(orh_whatif* job);
  * routes, reduced on the device while the request's row is still in its
  * buffer (a job's rows are far too many to copy out: C4 is 105 GB).
  * Request i's row (d_dist + i*N, d_nh + i*N, one mask word per node: the rows
- * an orh_whatif_run / _run_drains of this job wrote) is compared with the
+ * an orh_whatif_run / _run_drains / _run_metrics of this job wrote) is compared with the
  * job's base row of source h_src_idx[i] (orh_whatif_base_rows), node by node.
  * A node unreached in the base row is in no class, and neither is the
  * request's source. */

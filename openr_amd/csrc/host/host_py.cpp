@@ -688,6 +688,17 @@ py::tuple nodeImpactArrays(const Job& b, size_t n) {
   return py::make_tuple(lost, moved);
 }
 
+// what_if_batch(metric=...): per request a list of (link_id, from_name or
+// None for both ends, new_metric)
+using PyMetricRaises = std::vector<std::vector<std::tuple<uint32_t, std::optional<std::string>, uint32_t>>>;
+
+std::vector<std::vector<WhatIfMetricRaise>> metricRaises(const PyMetricRaises& in) {
+  std::vector<std::vector<WhatIfMetricRaise>> out(in.size());
+  for (size_t i = 0; i < in.size(); ++i)
+    for (const auto& [link, from, metric] : in[i]) out[i].push_back({link, from ? *from : std::string(), metric});
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_openr_host, m) {
@@ -949,14 +960,17 @@ PYBIND11_MODULE(_openr_host, m) {
       .def("what_if_batch",  // a what-if job over `srcs`: request i = (srcs[src_idx[i]], ignore[i])
            [](const LinkState& s, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric,
-              bool shareBase, bool searchLarge, const std::optional<std::vector<std::vector<std::string>>>& drain) {
+              bool shareBase, bool searchLarge, const std::optional<std::vector<std::vector<std::string>>>& drain,
+              const std::optional<PyMetricRaises>& metric) {
              // drain: per request the node names it treats as overloaded (None: no drains)
+             // metric: per request its (link_id, from_name_or_None, new_metric) raises (None: none)
              return new WhatIfBatch(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase, searchLarge,
-                                    drain ? *drain : std::vector<std::vector<std::string>>{});
+                                    drain ? *drain : std::vector<std::vector<std::string>>{},
+                                    metric ? metricRaises(*metric) : std::vector<std::vector<WhatIfMetricRaise>>{});
            },
            py::arg("srcs"), py::arg("src_idx"), py::arg("ignore"), py::arg("chunk") = 4096,
            py::arg("use_link_metric") = true, py::arg("share_base") = false, py::arg("search_large") = false,
-           py::arg("drain") = py::none(),
+           py::arg("drain") = py::none(), py::arg("metric") = py::none(),
            py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
       .def("run_spf_batch",
            [](const LinkState& s, const std::vector<std::string>& srcs,
@@ -1052,13 +1066,15 @@ PYBIND11_MODULE(_openr_host, m) {
       .def("what_if_batch",
            [](const ReplicatedLinkState& s, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric,
-              bool shareBase, const std::optional<std::vector<std::vector<std::string>>>& drain) {
+              bool shareBase, const std::optional<std::vector<std::vector<std::string>>>& drain,
+              const std::optional<PyMetricRaises>& metric) {
              return new MultiDeviceWhatIf(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase,
-                                          drain ? *drain : std::vector<std::vector<std::string>>{});
+                                          drain ? *drain : std::vector<std::vector<std::string>>{},
+                                          metric ? metricRaises(*metric) : std::vector<std::vector<WhatIfMetricRaise>>{});
            },
            py::arg("srcs"), py::arg("src_idx"), py::arg("ignore"), py::arg("chunk") = 4096,
            py::arg("use_link_metric") = true, py::arg("share_base") = false, py::arg("drain") = py::none(),
-           py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
+           py::arg("metric") = py::none(), py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
       .def("kth_paths_batch",
            [](const ReplicatedLinkState& s, const std::vector<std::pair<std::string, std::string>>& pairs) {
              return new MultiDeviceKthPaths(s, pairs);

@@ -19,7 +19,8 @@ void check(orh_ctx* ctx, int rc, const char* what) {
 WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& srcs,
                          const std::vector<uint32_t>& srcIdx, const std::vector<std::vector<uint32_t>>& ignore,
                          uint32_t chunk, bool useLinkMetric, bool shareBase, bool searchLarge,
-                         const std::vector<std::vector<std::string>>& drain)
+                         const std::vector<std::vector<std::string>>& drain,
+                         const std::vector<std::vector<WhatIfMetricRaise>>& metric)
     : ls_(ls), useLinkMetric_(useLinkMetric), shareBase_(shareBase), searchLarge_(searchLarge) {
   if (srcIdx.size() != ignore.size()) throw std::invalid_argument("WhatIfBatch: one ignore set per request");
   if (!drain.empty() && drain.size() != srcIdx.size())
@@ -31,6 +32,20 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
       if (!id) throw std::invalid_argument("WhatIfBatch: unknown drained node " + name);
       drainIds[i].push_back(*id);
       drains_ = true;
+    }
+  if (!metric.empty() && metric.size() != srcIdx.size())
+    throw std::invalid_argument("WhatIfBatch: one list of metric raises per request (or none at all)");
+  std::vector<std::vector<orh_whatif_metric>> raiseIds(metric.size());
+  for (size_t i = 0; i < metric.size(); ++i)
+    for (const auto& mr : metric[i]) {
+      uint32_t from = ORH_NO_NODE;
+      if (!mr.from.empty()) {
+        auto id = ls.nodeId(mr.from);
+        if (!id) throw std::invalid_argument("WhatIfBatch: unknown node " + mr.from + " in a metric raise");
+        from = *id;
+      }
+      raiseIds[i].push_back({mr.link, from, mr.metric});
+      raises_ = true;
     }
   if (chunk == 0) throw std::invalid_argument("WhatIfBatch: chunk must be positive");
   for (const auto& s : srcs) {
@@ -46,7 +61,8 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
   chunk_ = static_cast<uint32_t>(std::min<size_t>(chunk, std::max<size_t>(n, 1)));
   for (size_t c0 = 0; c0 < n; c0 += chunk_) {
     const size_t c1 = std::min(n, c0 + chunk_);
-    std::vector<uint32_t> ptr{0}, links, dptr, dnodes;
+    std::vector<uint32_t> ptr{0}, links, dptr, dnodes, mptr;
+    std::vector<orh_whatif_metric> mets;
     for (size_t i = c0; i < c1; ++i) {
       links.insert(links.end(), ignore[i].begin(), ignore[i].end());
       ptr.push_back(static_cast<uint32_t>(links.size()));
@@ -60,7 +76,16 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
       }
       if (dnodes.empty()) dnodes.push_back(0);
     }
-    chunks_.push_back({c0, c1, std::move(ptr), std::move(links), std::move(dptr), std::move(dnodes)});
+    if (raises_) {
+      mptr.push_back(0);
+      for (size_t i = c0; i < c1; ++i) {
+        mets.insert(mets.end(), raiseIds[i].begin(), raiseIds[i].end());
+        mptr.push_back(static_cast<uint32_t>(mets.size()));
+      }
+      if (mets.empty()) mets.push_back({0u, ORH_NO_NODE, 0u});
+    }
+    chunks_.push_back({c0, c1, std::move(ptr), std::move(links), std::move(dptr), std::move(dnodes),
+                       std::move(mptr), std::move(mets)});
   }
   graph_ = ls.deviceGraph();
   ctx_ = ls.context();
@@ -248,7 +273,13 @@ void WhatIfBatch::run() {
     // this run overwrites the rows of chunk c - nBuf_, and waits for them by
     // itself: their summary goes right before it
     if (impact_ && c >= static_cast<size_t>(nBuf_)) queueImpact(c - nBuf_);
-    if (drains_)
+    if (raises_)
+      check(ctx_,
+            orh_whatif_run_metrics(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(),
+                                   drains_ ? ch.drnPtr.data() : nullptr, drains_ ? ch.drnNodes.data() : nullptr,
+                                   ch.metPtr.data(), ch.mets.data(), dDist_[b], dNh_[b], dInfo_ + ch.lo),
+            "orh_whatif_run_metrics");
+    else if (drains_)
       check(ctx_,
             orh_whatif_run_drains(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(),
                                   ch.drnPtr.data(), ch.drnNodes.data(), dDist_[b], dNh_[b], dInfo_ + ch.lo),

@@ -5,7 +5,9 @@
 // searched once, then the requests run in chunks into device row buffers; a
 // request's row is its source's row except below a tight ignored link or a
 // tight out-link of a drained node, where the job re-derives it (bit-identical
-// to a fresh runSpf).
+// to a fresh runSpf). A request may also raise link metrics (cost a link out,
+// Link::setMetricFromNode, :640-710): the same repair below the raised records
+// that were tight, with the raised weights.
 //
 // This is the library form a caller outside Python drives (the bench, the
 // multi-device split in multi_device.h); the Python binding wraps it.
@@ -19,6 +21,15 @@
 
 namespace openr_amd {
 
+// One metric raise of a what-if request (costing a link out): the metric
+// that `from` advertises for LinkState link `link` becomes `metric` (>= the
+// current one). An empty `from` raises it from both ends.
+struct WhatIfMetricRaise {
+  uint32_t link;
+  std::string from;
+  uint32_t metric;
+};
+
 class WhatIfBatch {
  public:
   // request i = (srcs[srcIdx[i]], ignore[i]) with ignore sets of LinkState link
@@ -28,11 +39,15 @@ class WhatIfBatch {
   // full: for a device's block of a split job). drain: per request the names
   // of the nodes it treats as overloaded (empty: no request drains any; else
   // one list per request, each possibly empty); an unknown name is
-  // std::invalid_argument
+  // std::invalid_argument. metric: per request its metric raises, with the
+  // same conventions (empty: none at all; an unknown end name is
+  // std::invalid_argument; a decrease fails the run, see
+  // orh_whatif_run_metrics)
   WhatIfBatch(const LinkState& ls, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric = true,
               bool shareBase = false, bool searchLarge = false,
-              const std::vector<std::vector<std::string>>& drain = {});
+              const std::vector<std::vector<std::string>>& drain = {},
+              const std::vector<std::vector<WhatIfMetricRaise>>& metric = {});
   ~WhatIfBatch();
   WhatIfBatch(const WhatIfBatch&) = delete;
   WhatIfBatch& operator=(const WhatIfBatch&) = delete;
@@ -84,6 +99,8 @@ class WhatIfBatch {
     size_t lo, hi;
     std::vector<uint32_t> ptr, links;
     std::vector<uint32_t> drnPtr, drnNodes;  // drained node ids, rebased like the ignore CSR
+    std::vector<uint32_t> metPtr;            // metric raises, rebased the same way
+    std::vector<orh_whatif_metric> mets;
   };
   void allocate();
   const LinkState& ls_;
@@ -92,6 +109,7 @@ class WhatIfBatch {
   bool searchLarge_;
   bool digests_{false};
   bool drains_{false};  // some request drains a node: runs go through orh_whatif_run_drains
+  bool raises_{false};  // some request raises a metric: runs go through orh_whatif_run_metrics
   std::vector<uint32_t> srcs_, srcIdx_;
   std::vector<Chunk> chunks_;
   uint32_t chunk_{1};

@@ -24,7 +24,9 @@ namespace orh {
 //   tier 3 global slots sized for the whole graph (cannot overflow)
 //   tier 4 only without slots: the full HBM search (fallback flags)
 // A request may also drain nodes (treat them as overloaded): their
-// out-records are staged as cuts, drn_ptr / drn carry the sets.
+// out-records are staged as cuts, drn_ptr / drn carry the sets. A request may
+// raise link metrics too: the raised records are staged as cuts, rse_ptr /
+// rse carry (record, new weight); a run with raises takes no full search.
 constexpr uint32_t kWhatifTierBase = 0, kWhatifTierSmall = 1, kWhatifTierLarge = 2, kWhatifTierSlot = 3,
                    kWhatifTierSearch = 4;
 constexpr uint32_t kSmallA = 256, kSmallE = 1024;
@@ -51,12 +53,17 @@ struct RepairArgs {
   const uint32_t* ign;        // sorted per request
   const uint32_t* cut_ptr;    // [n_req + 1]
   const uint4* cuts;          // (tail, head, record tail -> head, 0) per ignored link end, and per
-                              // out-record of a drained node
+                              // out-record of a drained node, and per raised record
   // drained nodes (nullable: none, and the kernels without the drain tests
   // run): per request the nodes treated as overloaded, sorted, without the
   // request's source
   const uint32_t* drn_ptr;    // [n_req + 1]
   const uint32_t* drn;
+  // metric raises (nullable: none, and the kernels without the raise lookup
+  // run): per request (record index, raised weight) pairs sorted by record;
+  // each raised record is staged as a cut as well
+  const uint32_t* rse_ptr;    // [n_req + 1]
+  const uint2* rse;
   uint32_t* out_dist;         // [n_req][N]
   uint32_t* out_nh;           // [n_req][N], one mask word
   uint32_t* fallback;         // [n_req] set when a request needs the full search (no slots)

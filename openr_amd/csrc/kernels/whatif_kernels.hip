@@ -55,6 +55,30 @@
 // instantiated with and without the drain tests (kDrain); a run without
 // drains launches the code it always did. Tier 4's full search honours the
 // set through SpfArgs::drain_ptr (spf_hbm_kernels.hip, its own kDrain).
+//
+// Metric raises (orh_whatif_run_metrics): a request may also raise the metric
+// one end of a link advertises (Link::setMetricFromNode, LinkState.cpp:640-710:
+// costing a link out). An ignored link is a metric raised to infinity, and the
+// argument above needs only that relaxations get weaker: with w the record's
+// own weight and w' >= w the raised one, the host stages one cut (tail, head,
+// record) per raised record next to the ignore and drain cuts, and a sorted
+// per-request list (record, w'). Then
+//
+//   seeds    as before: heads of the cut records that are tight in the base
+//            row under the OLD weight w (tail a transit node)
+//   closure  unchanged, under the old weights
+//   pred     an ignored link is skipped (ignore wins over a raise of the same
+//            link); else the edge weighs w' when the request raises that
+//            record, w otherwise - inside A and at its boundary alike
+//
+// A node outside A keeps every tight predecessor at its old weight (a raised
+// tight record's head is a seed), no label got smaller anywhere, so its row
+// entry stands; inside A the fixpoint over the reweighted predecessor edges is
+// unique as before. Templated on kRaise like kDrain: a run without raises
+// launches the instantiations it always did. The full search is not taught
+// about raises: a run that stages any takes none (the host leaves full_cap 0
+// and refuses a graph without slots), so tier 3, whose state is sized for the
+// whole graph, ends every such request.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,6 +111,19 @@ __device__ inline unsigned long long meet(unsigned long long l, uint64_t d, uint
 __device__ inline void bar() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+}
+
+// the request's raised weight of record `rec`, else w: (record, new weight)
+// pairs sorted by record, a few entries; callers test n != 0 first
+__device__ inline uint32_t raised(const uint2* rse, uint32_t n, uint32_t rec, uint32_t w) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    const uint2 x = rse[mid];
+    if (x.x == rec) return x.y;
+    if (x.x < rec) lo = mid + 1; else hi = mid;
+  }
+  return w;
 }
 
 // visit the live records of node v: ELL slots then the overflow list
@@ -146,7 +183,7 @@ __global__ __launch_bounds__(256) void whatif_copy_kernel(RepairArgs a, uint32_t
 // caps cap_a / cap_e (LDS, or a global slot with whole-graph caps). Returns
 // |A|, or ~0u when A or its edge list outgrows the caps. The membership
 // bitmap must be all zero on entry; the caller clears it afterwards.
-template <int K, bool kDrain>
+template <int K, bool kDrain, bool kRaise>
 __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, uint32_t cap_a, uint32_t cap_e,
                                uint32_t* s_cnt, uint32_t* s_ecnt, uint32_t* s_ovf, uint32_t* s_flag) {
   const uint32_t N = a.n_nodes;
@@ -176,6 +213,14 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
     drn = a.drn + a.drn_ptr[r];
     n_drn = a.drn_ptr[r + 1] - a.drn_ptr[r];
   }
+  // the request's raised records (sorted by record): read-only global memory,
+  // in the slot pass too, so no barrier orders it
+  const uint2* rse = nullptr;
+  uint32_t n_rse = 0;
+  if constexpr (kRaise) {
+    rse = a.rse + a.rse_ptr[r];
+    n_rse = a.rse_ptr[r + 1] - a.rse_ptr[r];
+  }
 
   if (tid == 0) {
     *s_cnt = 0u;
@@ -193,7 +238,8 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
     else *s_ovf = 1u;
   };
   // seeds: heads of tight ignored records whose tail is a transit node (a
-  // drained node's out-records are staged as cuts of their own)
+  // drained node's out-records and the raised records are staged as cuts of
+  // their own; tight means tight under the record's own, old weight)
   for (uint32_t c = a.cut_ptr[r] + tid; c < a.cut_ptr[r + 1]; c += B) {
     const uint4 cut = a.cuts[c];  // (tail, head, record of tail -> head, 0)
     const uint2 rec = a.recs[cut.z];
@@ -242,7 +288,9 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
     if (p != s && (back.x & ORH_REC_ROW_OVL)) return;
     if constexpr (kDrain)
       if (n_drn && p != s && drained(drn, n_drn, p)) return;
-    const uint32_t w = metric ? back.y : 1u;
+    uint32_t w = metric ? back.y : 1u;
+    if constexpr (kRaise)
+      if (n_rse) w = raised(rse, n_rse, q2, w);  // staged for metric jobs only
     if (bits[p >> 5] & (1u << (p & 31u))) inside(p, w);
     else outside(p, q2, w);
   };
@@ -355,7 +403,7 @@ __global__ __launch_bounds__(256) void whatif_seed_kernel(RepairArgs a) {
 // slot per workgroup (tier 3); a request that outgrows the caps moves on to
 // the next queue. Every workgroup leaves once its claim passes the queue's
 // length (fixed before this launch by the previous kernel).
-template <int K, uint32_t kTier, bool kDrain>
+template <int K, uint32_t kTier, bool kDrain, bool kRaise>
 __global__ __launch_bounds__(kTier == kWhatifTierSmall ? 128 : kTier == kWhatifTierLarge ? 256 : kSlotBlock)
 void whatif_repair_kernel(RepairArgs a, uint32_t cap_a, uint32_t cap_e, uint32_t q) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -381,7 +429,7 @@ void whatif_repair_kernel(RepairArgs a, uint32_t cap_a, uint32_t cap_e, uint32_t
     bar();
     const uint32_t r = s_req;
     if (r == ~0u) break;
-    const uint32_t n = repair_one<K, kDrain>(a, r, base, cap_a, cap_e, &s_cnt, &s_ecnt, &s_ovf, s_flag);
+    const uint32_t n = repair_one<K, kDrain, kRaise>(a, r, base, cap_a, cap_e, &s_cnt, &s_ecnt, &s_ovf, s_flag);
     if (tid == 0) {
       if (n != ~0u) {
         if (a.info) a.info[r] = kTier | (n << 3);
@@ -456,7 +504,8 @@ hipError_t launch_repair_back(const RepairArgs& a, uint32_t ell_k, size_t lds_li
 namespace {
 
 // one tier's launch: the instantiation for the graph's ELL width, with the
-// drain tests only when the run stages drained nodes
+// drain tests only when the run stages drained nodes and the raised weights
+// only when it stages metric raises
 template <uint32_t kTier>
 hipError_t launch_tier(const RepairArgs& a, uint32_t ell_k, uint32_t grid, uint32_t block, size_t lds,
                        hipStream_t s, uint32_t cap_a, uint32_t cap_e, uint32_t q) {
@@ -464,9 +513,18 @@ hipError_t launch_tier(const RepairArgs& a, uint32_t ell_k, uint32_t grid, uint3
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, s, a, cap_a, cap_e, q);
     return hipGetLastError();
   };
+  if (a.rse_ptr) {
+    if (a.drn_ptr)
+      return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, true, true>)
+                        : go(whatif_repair_kernel<4, kTier, true, true>);
+    return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, false, true>)
+                      : go(whatif_repair_kernel<4, kTier, false, true>);
+  }
   if (a.drn_ptr)
-    return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, true>) : go(whatif_repair_kernel<4, kTier, true>);
-  return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, false>) : go(whatif_repair_kernel<4, kTier, false>);
+    return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, true, false>)
+                      : go(whatif_repair_kernel<4, kTier, true, false>);
+  return ell_k == 8 ? go(whatif_repair_kernel<8, kTier, false, false>)
+                    : go(whatif_repair_kernel<4, kTier, false, false>);
 }
 
 }  // namespace

@@ -1606,14 +1606,80 @@ int whatif_stage(orh_whatif* job, size_t words, uint32_t** h, uint32_t** d) {
 // context stream through side_ev
 // drn_ptr / drn_nodes (nullable: none): per request the nodes it drains, i.e.
 // treats as overloaded (orh_whatif_run_drains)
+// met_ptr / mets (nullable: none): per request the metrics it raises
+// (orh_whatif_run_metrics); resolved here to records, each a cut and an entry
+// of the request's sorted (record, raised weight) list
+struct StagedRaise {
+  uint32_t rec, w, tail, head, old;  // record, raised weight, its ends, its own weight
+};
+
 int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const uint32_t* ign_ptr,
-               const uint32_t* ign_links, const uint32_t* drn_ptr, const uint32_t* drn_nodes, uint32_t* d_dist,
-               uint32_t* d_nh, uint32_t* d_info) {
+               const uint32_t* ign_links, const uint32_t* drn_ptr, const uint32_t* drn_nodes,
+               const uint32_t* met_ptr, const orh_whatif_metric* mets, uint32_t* d_dist, uint32_t* d_nh,
+               uint32_t* d_info) {
   orh_graph* g = job->g;
   orh_ctx* ctx = g->ctx;
   const uint32_t N = g->n_nodes, m = static_cast<uint32_t>(job->srcs.size());
   for (uint32_t i = 0; i < n_req; ++i)
     if (src_idx[i] >= m) return fail(ctx, ORH_E_INVALID, "orh_whatif_run: source index out of range");
+  // metric raises, validated and resolved before anything is queued: per
+  // request its effective raises sorted by record, the largest of a repeated
+  // (link, end) kept. A hop-count job checks them and stages none
+  std::vector<uint32_t> rse_ptr;
+  std::vector<StagedRaise> rse;
+  if (met_ptr) {
+    const std::vector<uint32_t>& erow = entry_rows(g);
+    rse_ptr.assign(size_t{n_req} + 1, 0u);
+    for (uint32_t i = 0; i < n_req; ++i) {
+      const size_t r0 = rse.size();
+      for (uint32_t k = met_ptr[i]; k < met_ptr[i + 1]; ++k) {
+        const orh_whatif_metric& mr = mets[k];
+        if (mr.link >= g->n_links) continue;  // as ignore sets do
+        const uint32_t ent[2] = {g->link_ent[2 * static_cast<size_t>(mr.link)],
+                                 g->link_ent[2 * static_cast<size_t>(mr.link) + 1]};
+        if (ent[0] == ~0u && ent[1] == ~0u) continue;  // a free slot
+        bool end_ok = mr.from_node == ORH_NO_NODE, down = false;
+        for (uint32_t e : ent)
+          if (e != ~0u) {
+            end_ok |= erow[e] == mr.from_node;
+            down |= (g->meta[e] & ORH_META_DOWN) != 0;
+          }
+        if (!end_ok)
+          return fail(ctx, ORH_E_INVALID, "orh_whatif_run_metrics: from_node is not an end of the link");
+        if (down) continue;  // never on a path, whatever it costs
+        for (uint32_t e : ent) {
+          if (e == ~0u || (mr.from_node != ORH_NO_NODE && erow[e] != mr.from_node)) continue;
+          if (mr.metric < g->w_out[e])
+            return fail(ctx, ORH_E_INVALID,
+                        "orh_whatif_run_metrics: metric below the current one (a decrease is a topology change)");
+          if (mr.metric == g->w_out[e] || !job->use_link_metric) continue;
+          rse.push_back({g->pos[e], mr.metric, erow[e], g->col[e], g->w_out[e]});
+        }
+      }
+      std::sort(rse.begin() + static_cast<ptrdiff_t>(r0), rse.end(), [](const StagedRaise& x, const StagedRaise& y) {
+        return x.rec != y.rec ? x.rec < y.rec : x.w > y.w;
+      });
+      rse.erase(std::unique(rse.begin() + static_cast<ptrdiff_t>(r0), rse.end(),
+                            [](const StagedRaise& x, const StagedRaise& y) { return x.rec == y.rec; }),
+                rse.end());
+      rse_ptr[i + 1] = static_cast<uint32_t>(rse.size());
+    }
+    if (!rse.empty()) {
+      // rows are u32: the job's distance bound (whatif_plan) plus what one
+      // request adds to a path must stay below the unreached mark
+      for (uint32_t i = 0; i < n_req; ++i) {
+        uint64_t add = 0;
+        for (uint32_t k = rse_ptr[i]; k < rse_ptr[i + 1]; ++k) add += rse[k].w - rse[k].old;
+        if (job->bound + add >= 0xFFFFFFFFull)
+          return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_run_metrics: raised distances may exceed 32 bits");
+      }
+      const size_t sb = orh::repair_slot_bytes(N, g->n_recs);
+      if (kRepairSlotBudget / std::max<size_t>(sb, 1) == 0)
+        return fail(ctx, ORH_E_UNSUPPORTED,
+                    "orh_whatif_run_metrics: no repair slot fits this graph, and the full search takes no raises");
+    }
+  }
+  const bool raises = !rse.empty();  // else: exactly the run without the lists
   // staging: base_row[n] | srcs[n] | ign_ptr[n+1] | ign[..] | with drains: drn_ptr[n+1] | drn[..] |
   //          cut_ptr[n+1] | (pad to 16 B) cuts uint4[..]
   const uint32_t n_ign = ign_ptr[n_req];
@@ -1630,11 +1696,15 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
     if (x >= N) return fail(ctx, ORH_E_INVALID, "orh_whatif_run_drains: drained node out of range");
     n_cuts += g->row_ptr[x + 1] - g->row_ptr[x];
   }
+  n_cuts += rse.size();  // one cut per raised record
   const size_t off_src = n_req, off_ip = 2 * size_t{n_req}, off_ign = off_ip + n_req + 1;
   const size_t off_dp = off_ign + n_ign, off_drn = off_dp + n_req + 1;
   const size_t off_cp = drn_ptr ? off_drn + n_drn : off_ign + n_ign;
   const size_t off_cuts = (off_cp + n_req + 1 + 3) & ~size_t{3};
-  const size_t words = off_cuts + 4 * n_cuts + 4;
+  // with raises, behind the cuts: rse_ptr[n+1] | (pad to 8 B) rse uint2[..]
+  const size_t off_rp = off_cuts + 4 * n_cuts;
+  const size_t off_rse = (off_rp + n_req + 1 + 1) & ~size_t{1};
+  const size_t words = (raises ? off_rse + 2 * rse.size() : off_rp) + 4;
   {
     // slot `cur` is reused: its previous run's side part must be done (the
     // context stream waits); so must the other slot's when it writes rows
@@ -1699,8 +1769,16 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
       nd += dl;
       h[off_dp + i + 1] = static_cast<uint32_t>(nd);
     }
+    if (raises) {
+      uint2* hr = reinterpret_cast<uint2*>(h + off_rse);
+      for (uint32_t k = rse_ptr[i]; k < rse_ptr[i + 1]; ++k) {
+        cuts[nc++] = make_uint4(rse[k].tail, rse[k].head, rse[k].rec, 0u);
+        hr[k] = make_uint2(rse[k].rec, rse[k].w);
+      }
+    }
     hc[i + 1] = static_cast<uint32_t>(nc);
   }
+  if (raises) std::memcpy(h + off_rp, rse_ptr.data(), (size_t{n_req} + 1) * 4);
   const int c = job->cur;
   job->cur = (job->cur + 1) % kRunSlots;
   ORH_HIP(ctx, hipMemcpyAsync(d, h, words * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1738,7 +1816,12 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
     // 8 / 16 / 32 behind tier 2: profiles/r06/ab_search_cap.txt
     return e && atoi(e) > 0 ? static_cast<uint32_t>(atoi(e)) : 256u;
   }();
-  const uint32_t full_n = full_env ? full_env : (job->flags & ORH_WHATIF_SEARCH_LARGE) ? large_cap : 0u;
+  // a run with raises takes no full search (the search knows no raised
+  // weights): its slot tier ends every request
+  const uint32_t full_n = raises ? 0u
+                          : full_env ? full_env
+                          : (job->flags & ORH_WHATIF_SEARCH_LARGE) ? large_cap
+                                                                    : 0u;
   const bool split = n_slots && full_n == 0 && t3_split;
   if (split) {
     // run slot c's own slot memory, grown only with its stream idle
@@ -1783,6 +1866,10 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
   if (drn_ptr) {
     ra.drn_ptr = d + off_dp;
     ra.drn = d + off_drn;
+  }
+  if (raises) {
+    ra.rse_ptr = d + off_rp;
+    ra.rse = reinterpret_cast<const uint2*>(d + off_rse);
   }
   ra.cut_ptr = d + off_cp;
   ra.cuts = reinterpret_cast<const uint4*>(d + off_cuts);
@@ -2131,7 +2218,8 @@ int run_repair(orh_graph* g, const orh_spf_request* req, uint32_t* d_dist, uint3
   int rc = whatif_create(g, base_srcs.data(), static_cast<uint32_t>(base_srcs.size()), req->use_link_metric, &job);
   if (rc) return rc;
   ORH_HIP(ctx, hipEventRecord(ctx->evm, ctx->stream));
-  rc = whatif_run(job, n_src, base_row.data(), req->h_ignore_ptr, req->h_ignore_links, nullptr, nullptr, d_dist,
+  rc = whatif_run(job, n_src, base_row.data(), req->h_ignore_ptr, req->h_ignore_links, nullptr, nullptr, nullptr,
+                  nullptr, d_dist,
                   d_nh, nullptr);
   if (!rc) rc = whatif_flush(job);
   if (rc) {
@@ -2172,7 +2260,8 @@ int orh_whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, c
   if (job->gen != job->g->gen)
     return fail(ctx, ORH_E_STATE, "orh_whatif_run: the graph changed since the job was created");
   hipSetDevice(ctx->device);
-  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, nullptr, nullptr, d_dist, d_nh, d_info);
+  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, nullptr, nullptr, nullptr, nullptr, d_dist,
+                    d_nh, d_info);
 }
 
 int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
@@ -2188,8 +2277,27 @@ int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src
   if (job->gen != job->g->gen)
     return fail(ctx, ORH_E_STATE, "orh_whatif_run_drains: the graph changed since the job was created");
   hipSetDevice(ctx->device);
-  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes, d_dist, d_nh,
-                    d_info);
+  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes, nullptr,
+                    nullptr, d_dist, d_nh, d_info);
+}
+
+int orh_whatif_run_metrics(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
+                           const uint32_t* h_ignore_links, const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
+                           const uint32_t* h_metric_ptr, const orh_whatif_metric* h_metrics, uint32_t* d_dist,
+                           uint32_t* d_nh, uint32_t* d_info) {
+  if (!job) return ORH_E_INVALID;
+  orh_ctx* ctx = job->g->ctx;
+  join_deferred(ctx);
+  if (n_req == 0) return ORH_OK;
+  if (!h_src_idx || !h_ignore_ptr || (h_ignore_ptr[n_req] && !h_ignore_links) ||
+      (h_drain_ptr && h_drain_ptr[n_req] && !h_drain_nodes) ||
+      (h_metric_ptr && h_metric_ptr[n_req] && !h_metrics) || !d_dist || !d_nh)
+    return fail(ctx, ORH_E_INVALID, "orh_whatif_run_metrics: null argument");
+  if (job->gen != job->g->gen)
+    return fail(ctx, ORH_E_STATE, "orh_whatif_run_metrics: the graph changed since the job was created");
+  hipSetDevice(ctx->device);
+  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes, h_metric_ptr,
+                    h_metrics, d_dist, d_nh, d_info);
 }
 
 int orh_whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* d_dist,

@@ -155,6 +155,27 @@ def c4_drain_job(node_names: List[str], n_nodes: int = C4_WHATIF_LINKS, n_srcs: 
     return srcs, idx, ignore, drain
 
 
+def c4_costout_job(links, adj_dbs, node_names: List[str], n_links: int = C4_WHATIF_LINKS,
+                   n_srcs: int = C4_WHATIF_SRCS, factor: int = 10, seed: int = C4_SEED):
+    """The cost-out analogue of c4_what_if_job: "where does traffic go if this
+    link's metric is raised x factor from both ends?" for the link job's links
+    and sources. links: (link id, (node1, if1, node2, if2)) pairs as
+    LinkState.link_ids() gives them; adj_dbs: the loaded adjacency databases
+    (each end's current metric). Returns (sources, per request its source
+    index, per request its (empty) ignore set, per request its raises
+    [(link id, end name, new metric)] - one per end, each end's own metric
+    times factor)."""
+    desc = dict(links)
+    srcs, idx, sets = c4_what_if_job([lid for lid, _ in links], node_names, n_links, n_srcs, seed)
+    cur = {(db.thisNodeName, a.ifName): a.metric for db in adj_dbs for a in db.adjacencies}
+    ignore = [[] for _ in sets]
+    metric = []
+    for (lid,) in sets:
+        n1, if1, n2, if2 = desc[lid]
+        metric.append([(lid, n1, cur[(n1, if1)] * factor), (lid, n2, cur[(n2, if2)] * factor)])
+    return srcs, idx, ignore, metric
+
+
 def c4_node_weights(node_names: List[str], seed: int = C4_SEED, max_prefixes: int = 64):
     """Seeded per-node weights for what-if impact summaries on the C4 WAN: the
     prefixes each node advertises, uniform in [0, max_prefixes], as
