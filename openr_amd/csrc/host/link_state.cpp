@@ -746,6 +746,9 @@ void LinkState::prefetchSpfResults(const std::vector<std::string>& nodes,
   auto rows = runSpfBatch(ids, useLinkMetric, nullptr);
   for (auto& r : rows) {
     std::string name = r.srcName;
+    // a KSP2 batch counted this source's run already (another pair of its was
+    // flagged for the host in the same or a later batch)
+    if (useLinkMetric && countedOnDevice_.erase(name)) --spfRuns_;
     spfResults_.emplace(std::make_pair(std::move(name), useLinkMetric), std::move(r));
   }
 }

@@ -286,6 +286,31 @@ def test_multi_device_ksp2_c4_union(hip, replicas):
             assert mk.paths(i, k) == ls.get_kth_path_ids(s, d, k), (i, s, d, k)
 
 
+def test_multi_device_ksp2_flagged_pairs(hip):
+    """The 612-node ring batch of test_gpu_ksp2_edges.py (pairs on both sides
+    of the wave kernel's 512 frames, one flagged in k = 1 and three in k = 2)
+    over two contexts: every pair equals the single LinkState's getKthPaths -
+    the flagged ones a replica traces itself included - and the device pairs
+    are the batch less the flagged ones."""
+    import ksp2_shapes
+    sh = ksp2_shapes.ring()
+    als, _ = load_topology(hip, sh["dbs"], [])
+    ls = als[A]._impl
+    ls.prefetch_kth_paths(sh["pairs"])
+    n, flagged = len(sh["pairs"]), len(sh["host_wave"])
+    assert ls.ksp_stats() == (n - flagged, flagged)
+    rls = _replicated(hip, sh["dbs"], [0, 0])
+    mk = rls.kth_paths_batch(sh["pairs"])
+    per_block = [mk.block_pairs(r) for r in range(2)]
+    assert mk.blocks == 2 and sum(per_block) == n and min(per_block) > 0
+    mk.run()
+    assert mk.device_pairs == n - flagged
+    for i, (s, d) in enumerate(sh["pairs"]):
+        for k in (1, 2):
+            assert mk.paths(i, k) == ls.get_kth_path_ids(s, d, k), (i, s, d, k)
+    assert [len(p) for p in mk.paths(sh["pairs"].index(("r0", "r100")), 2)] == [512]
+
+
 @pytest.mark.parametrize("best_route", [False, True])
 def test_sharded_route_builder_c3(hip, oracle, best_route):
     """C3's 100k-prefix buildRouteDb sharded over 8 device contexts
