@@ -951,12 +951,12 @@ PYBIND11_MODULE(_openr_host, m) {
                if (s.linkAlive(lid)) out.append(py::make_tuple(lid, linkDesc(s.link(lid))));
              return out;
            })
-      .def("what_if_sweep",  // runSpf(src, true, {links}) for many (src, ignore set) pairs
+      .def("what_if_sweep",  // runSpf(src, use_link_metric, {links}) for many (src, ignore set) pairs
            [](const LinkState& s, const std::vector<std::string>& srcs,
-              const std::vector<std::vector<uint32_t>>& ignore) {
-             return new SpfSweep(s, srcs, true, &ignore);
+              const std::vector<std::vector<uint32_t>>& ignore, bool useLinkMetric) {
+             return new SpfSweep(s, srcs, useLinkMetric, &ignore);
            },
-           py::keep_alive<0, 1>())
+           py::arg("srcs"), py::arg("ignore"), py::arg("use_link_metric") = true, py::keep_alive<0, 1>())
       .def("what_if_batch",  // a what-if job over `srcs`: request i = (srcs[src_idx[i]], ignore[i])
            [](const LinkState& s, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric,
