@@ -96,9 +96,8 @@ size_t repair_lds_bytes(uint32_t n_nodes, uint32_t cap_a, uint32_t cap_e);
 // bytes of one global repair slot (whole-graph caps)
 size_t repair_slot_bytes(uint32_t n_nodes, uint32_t n_recs);
 // seed, copy each request's base rows, then the repair tiers; with no slots
-// the requests that outgrow tier 2 get fallback[r] = 1 (zeroed beforehand)
-hipError_t launch_repair(const RepairArgs& a, uint32_t ell_k, size_t lds_limit, hipStream_t s);
-// the same in two parts: seed and copy (HBM-bound, the whole GPU), then the
+// the requests that outgrow tier 2 get fallback[r] = 1 (zeroed beforehand).
+// In two parts: seed and copy (HBM-bound, the whole GPU), then the
 // repair tiers (latency-bound, a few thousand workgroups), which may run on a
 // second stream, overlapping the next batch's copy
 hipError_t launch_repair_front(const RepairArgs& a, uint32_t ell_k, size_t lds_limit, hipStream_t s);

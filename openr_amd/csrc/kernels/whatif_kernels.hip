@@ -527,48 +527,54 @@ hipError_t launch_tier(const RepairArgs& a, uint32_t ell_k, uint32_t grid, uint3
                     : go(whatif_repair_kernel<4, kTier, false, false>);
 }
 
+// Which tiers a run launches and which queue each drains; the one place that
+// knows it (the back launch and repair_slot_queue both read it). The seed
+// fills queue 0; a tier that runs moves what outgrows it to the next queue.
+struct TierPlan {
+  bool t1;            // tier 1 exists: its LDS state is smaller than tier 2's
+  bool t2;            // tier 2 runs (not with skip_large behind a tier 1)
+  uint32_t q2, qs;    // the queues tier 2 and the slot tier drain (tier 1: queue 0)
+  uint32_t sa, se;    // tier 1's caps
+  size_t lds1, lds2;  // LDS bytes of tiers 1 and 2
+};
+
+TierPlan tier_plan(const RepairArgs& a) {
+  TierPlan p{};
+  p.lds1 = tier1_lds(a, &p.sa, &p.se);
+  p.lds2 = repair_lds_bytes(a.n_nodes, a.cap_a, a.cap_e);
+  p.t1 = p.lds1 < p.lds2;
+  // skip_large: the slot tier (and the full searches) take tier 1's overflow
+  p.t2 = !(a.skip_large && p.t1);
+  p.q2 = p.t1 ? 1u : 0u;  // without the small tier, tier 2 drains queue 0 itself
+  p.qs = p.t2 ? p.q2 + 1u : p.q2;
+  return p;
+}
+
 }  // namespace
 
 hipError_t launch_repair_back_split(const RepairArgs& a, uint32_t ell_k, size_t lds_limit, hipStream_t s,
                                     hipStream_t s3, hipEvent_t mid) {
   if (a.n_req == 0) return hipSuccess;
   if (ell_k != 4 && ell_k != 8) return hipErrorInvalidValue;
-  uint32_t sa = 0, se = 0;
-  const size_t lds1 = tier1_lds(a, &sa, &se);
-  const size_t lds2 = repair_lds_bytes(a.n_nodes, a.cap_a, a.cap_e);
-  if (lds1 < lds2) {
-    const hipError_t e1 =
-        launch_tier<kWhatifTierSmall>(a, ell_k, tier_grid(a, lds_limit, lds1, 16), 128, lds1, s, sa, se, 0u);
-    if (e1 != hipSuccess) return e1;
-  }
-  // without the small tier, tier 2 drains queue 0 itself
-  const uint32_t q2 = lds1 < lds2 ? 1u : 0u;
-  // skip_large: the slot tier (and the full searches) take tier 1's overflow
-  const bool no_t2 = a.skip_large && lds1 < lds2;
+  const TierPlan p = tier_plan(a);
   hipError_t e = hipSuccess;
-  if (!no_t2) {
-    e = launch_tier<kWhatifTierLarge>(a, ell_k, tier_grid(a, lds_limit, lds2, 8), 256, lds2, s, a.cap_a, a.cap_e,
-                                      q2);
+  if (p.t1) {
+    e = launch_tier<kWhatifTierSmall>(a, ell_k, tier_grid(a, lds_limit, p.lds1, 16), 128, p.lds1, s, p.sa, p.se, 0u);
+    if (e != hipSuccess) return e;
+  }
+  if (p.t2) {
+    e = launch_tier<kWhatifTierLarge>(a, ell_k, tier_grid(a, lds_limit, p.lds2, 8), 256, p.lds2, s, a.cap_a, a.cap_e,
+                                      p.q2);
     if (e != hipSuccess) return e;
   }
   if (a.n_slots == 0) return e;
-  const uint32_t qs = no_t2 ? q2 : q2 + 1u;
   if (s3 != s) {
     if ((e = hipEventRecord(mid, s)) != hipSuccess || (e = hipStreamWaitEvent(s3, mid, 0)) != hipSuccess) return e;
   }
-  return launch_tier<kWhatifTierSlot>(a, ell_k, a.n_slots, kSlotBlock, 0, s3, a.n_nodes, a.n_recs, qs);
+  return launch_tier<kWhatifTierSlot>(a, ell_k, a.n_slots, kSlotBlock, 0, s3, a.n_nodes, a.n_recs, p.qs);
 }
 
-uint32_t repair_slot_queue(const RepairArgs& a) {
-  uint32_t sa = 0, se = 0;
-  const bool t1 = tier1_lds(a, &sa, &se) < repair_lds_bytes(a.n_nodes, a.cap_a, a.cap_e);
-  return t1 ? (a.skip_large ? 1u : 2u) : 1u;
-}
-
-hipError_t launch_repair(const RepairArgs& a, uint32_t ell_k, size_t lds_limit, hipStream_t s) {
-  hipError_t e = launch_repair_front(a, ell_k, lds_limit, s);
-  return e != hipSuccess ? e : launch_repair_back(a, ell_k, lds_limit, s);
-}
+uint32_t repair_slot_queue(const RepairArgs& a) { return tier_plan(a).qs; }
 
 namespace {
 

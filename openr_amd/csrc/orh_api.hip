@@ -1466,6 +1466,15 @@ constexpr uint32_t kRepairSlots = 64;       // tier 3: whole-graph state in glob
 constexpr size_t kRepairSlotBudget = 1ull << 30;  // bytes for all slots
 constexpr uint32_t kRepairMaxIgnore = 8;  // link-failure sets; KSP2 k = 2 sets are whole paths
 
+// Slot-tier workgroups of a run of n_req >= 1 requests: one slot each, as many
+// as the budget holds. 0: no slot fits this graph, and what outgrows tier 2 is
+// searched in full (tier 4); runs and impact summaries must agree on that
+static uint32_t repair_slots_for(uint32_t n_nodes, uint32_t n_recs, uint32_t n_req) {
+  const size_t slot_bytes = orh::repair_slot_bytes(n_nodes, n_recs);
+  return static_cast<uint32_t>(
+      std::min<size_t>(std::min<size_t>(kRepairSlots, n_req), kRepairSlotBudget / std::max<size_t>(slot_bytes, 1)));
+}
+
 // What-if search plan for the graph: the repair needs one mask word per
 // source, no zero metrics (the exact kernel's extraction order decides those
 // first hops) and a full-search plan for the no-slot fallback
@@ -1518,6 +1527,28 @@ static bool repair_eligible(orh_graph* g, const orh_spf_request* req, uint32_t w
 // staging and slot memory (and waits for its side part)
 constexpr int kRunSlots = 3;
 
+// request staging: pinned host words and their device copy (stage_acquire)
+struct StageBuf {
+  uint32_t* h = nullptr;
+  uint32_t* d = nullptr;
+  size_t cap = 0;           // u32, both sides
+  hipEvent_t ev = nullptr;  // upload done (and, on the context stream, what was queued before it)
+};
+
+// what one run slot owns, and the side-stream part of its last run
+struct RunSlot {
+  StageBuf stage;
+  uint32_t* d_work = nullptr;  // queues [3][n] | counters | fallback flags [n]
+  size_t work_cap = 0;            // bytes
+  hipEvent_t front_ev = nullptr;  // context-stream part done
+  hipEvent_t mid_ev = nullptr;    // tiers 1 and 2 done on `side` (split runs)
+  hipEvent_t side_ev = nullptr;   // side-stream part done
+  bool pending = false;           // side part not yet joined into the context stream
+  uintptr_t out_lo = 0, out_hi = 0;  // output span of that run (hazard checks)
+  uint8_t* t3_slots = nullptr;       // the slot memory of its split slot tier
+  size_t t3_slots_cap = 0;
+};
+
 struct orh_whatif {
   orh_graph* g = nullptr;
   uint64_t gen = 0;  // graph structure the base rows belong to
@@ -1527,22 +1558,11 @@ struct orh_whatif {
   std::vector<uint32_t> srcs;
   uint32_t* d_base = nullptr;  // dist rows [m][N], then mask rows [m][N]
   size_t base_cap = 0;         // bytes
-  // runs cycle through kRunSlots slots, each with its request staging (pinned
-  // host + device), its work queues / counters / fallback flags, and the
-  // side-stream part of its last run: the repair tiers of run r run on
-  // `side` (and t3[slot]) while run r + 1's seed / copy run on the context
+  // runs cycle through kRunSlots slots: the repair tiers of run r run on
+  // `side` (and t3[r % kT3]) while run r + 1's seed / copy run on the context
   // stream
   hipStream_t side = nullptr;
-  uint32_t* h_stage[kRunSlots] = {};
-  uint32_t* d_stage[kRunSlots] = {};
-  size_t stage_cap[kRunSlots] = {};  // u32, both sides
-  hipEvent_t stage_ev[kRunSlots] = {};  // upload done
-  uint32_t* d_work[kRunSlots] = {};     // queues [3][n] | counters | fallback flags [n]
-  size_t work_cap[kRunSlots] = {};
-  hipEvent_t front_ev[kRunSlots] = {};  // context-stream part done
-  hipEvent_t side_ev[kRunSlots] = {};   // side-stream part done
-  bool pending[kRunSlots] = {};             // side part not yet joined into the context stream
-  uintptr_t out_lo[kRunSlots] = {}, out_hi[kRunSlots] = {};  // output span of that run (hazard checks)
+  RunSlot run[kRunSlots];
   int cur = 0;
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;  // create .. last flush
   uint64_t requests = 0;
@@ -1550,12 +1570,12 @@ struct orh_whatif {
   uint8_t* own_slots = nullptr;
   size_t own_slots_cap = 0;
   // labels of the full searches that take the slot tier's largest repairs
-  // (side stream only, so one buffer serves both run slots)
+  // (side stream only, so one buffer serves every run slot)
   void* d_full_lab = nullptr;
   size_t full_lab_cap = 0;
   uint32_t flags = 0;  // ORH_WHATIF_* job flags
   // the slot tier of a run on a stream of its own (t3[run % kT3]), with its
-  // slot's memory, after event mid_ev[slot] (tiers 1 and 2 done on `side`):
+  // slot's memory, after event mid_ev (tiers 1 and 2 done on `side`):
   // the next run's small tiers start without waiting for its largest repairs
   // two streams, by run parity: with the context stream and `side` that is
   // HIP's 4 hardware queues (GPU_MAX_HW_QUEUES); a fifth stream would share
@@ -1563,202 +1583,273 @@ struct orh_whatif {
   static constexpr int kT3 = 2;
   hipStream_t t3[kT3] = {};
   uint64_t runs = 0;
-  hipEvent_t mid_ev[kRunSlots] = {};
-  uint8_t* t3_slots[kRunSlots] = {};
-  size_t t3_slots_cap[kRunSlots] = {};
   // orh_whatif_impact's request staging (base row | source node per request),
   // cycled like the run slots' but its own: an impact call is queued between
   // runs whose staging is still in flight
-  uint32_t* h_imp[kRunSlots] = {};
-  uint32_t* d_imp[kRunSlots] = {};
-  size_t imp_cap[kRunSlots] = {};     // u32, both sides
-  hipEvent_t imp_ev[kRunSlots] = {};  // upload done, and the kernels that read it
+  StageBuf imp[kRunSlots];
   int imp_cur = 0;
 };
 
 namespace {
 
-int whatif_stage(orh_whatif* job, size_t words, uint32_t** h, uint32_t** d) {
-  orh_ctx* ctx = job->g->ctx;
-  const int c = job->cur;
-  if (job->stage_ev[c]) ORH_HIP(ctx, hipEventSynchronize(job->stage_ev[c]));  // its last upload is done
-  if (words > job->stage_cap[c]) {
-    if (job->h_stage[c]) hipHostFree(job->h_stage[c]);
-    hipFree(job->d_stage[c]);
-    job->h_stage[c] = nullptr;
-    job->d_stage[c] = nullptr;
-    job->stage_cap[c] = 0;
-    const size_t cap = std::max<size_t>(words + words / 4, 4096);
-    ORH_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&job->h_stage[c]), cap * 4, hipHostMallocDefault));
-    ORH_HIP(ctx, hipMalloc(&job->d_stage[c], cap * 4));
-    job->stage_cap[c] = cap;
-  }
-  if (!job->stage_ev[c]) ORH_HIP(ctx, hipEventCreateWithFlags(&job->stage_ev[c], hipEventDisableTiming));
-  *h = job->h_stage[c];
-  *d = job->d_stage[c];
-  return ORH_OK;
+// The environment switches of the what-if runs, all read by whatif_knobs, once
+// per process. (ORH_REPAIR_CAPS is per context: orh_create reads it.)
+struct WhatifKnobs {
+  // ORH_WHATIF_FULL=n (A/B, default 0): the slot tier's queue goes to full
+  // searches first, up to n rows (labels within 1 GB). C4: 79 requests per
+  // job searched in full 30.7-31.2 ms against 29.6 ms in slots
+  // (profiles/r03/r_c4_full_search_ab.txt): the slots stay the default
+  uint32_t full;
+  // ORH_WHATIF_T3_SPLIT=0: the slot tier stays on `side` (A/B)
+  bool t3_split;
+  // ORH_WHATIF_SEARCH_CAP (256, A/B): the full searches per run of a job
+  // with ORH_WHATIF_SEARCH_LARGE. 256: tier 1's whole overflow of a C4 block
+  // (profiles/r06/an_skip_t2_ab/); 8 / 16 / 32 behind tier 2:
+  // profiles/r06/ab_search_cap.txt
+  uint32_t search_cap;
+  // ORH_WHATIF_SKIP_T2=0 keeps tier 2 (A/B). By default, with full searches,
+  // tier 1's overflow goes to them directly: tier 2 between them put its
+  // 0.4 ms on a short job's critical path (C4 block of 8: 5.34 -> 4.73 ms,
+  // profiles/r06/an_skip_t2_ab/)
+  bool skip_t2;
+};
+
+const WhatifKnobs& whatif_knobs() {
+  static const WhatifKnobs once = [] {
+    auto num = [](const char* name, int unset) {
+      const char* e = getenv(name);
+      return e ? atoi(e) : unset;
+    };
+    WhatifKnobs k{};
+    k.full = static_cast<uint32_t>(num("ORH_WHATIF_FULL", 0));
+    k.t3_split = num("ORH_WHATIF_T3_SPLIT", 1) != 0;
+    const int cap = num("ORH_WHATIF_SEARCH_CAP", 0);
+    k.search_cap = cap > 0 ? static_cast<uint32_t>(cap) : 256u;
+    k.skip_t2 = num("ORH_WHATIF_SKIP_T2", 1) != 0;
+    return k;
+  }();
+  return once;
 }
 
-// one batch of requests of a job: seed and copy and the small repair tiers
-// on the context stream; the large tiers, the slot tier (t3 streams) and,
-// without slots, the full search for what outgrew tier 2 on the job's side
-// streams, over job-owned memory (slots, labels), joined back into the
-// context stream through side_ev
-// drn_ptr / drn_nodes (nullable: none): per request the nodes it drains, i.e.
-// treats as overloaded (orh_whatif_run_drains)
-// met_ptr / mets (nullable: none): per request the metrics it raises
-// (orh_whatif_run_metrics); resolved here to records, each a cut and an entry
-// of the request's sorted (record, raised weight) list
+// One batch of requests of a job, as the three orh_whatif_run* entry points
+// pass it on
+struct WhatifRequests {
+  uint32_t n_req;
+  const uint32_t* src_idx;
+  const uint32_t *ign_ptr, *ign_links;
+  // nullable (none): per request the nodes it drains, i.e. treats as
+  // overloaded (orh_whatif_run_drains)
+  const uint32_t *drn_ptr, *drn_nodes;
+  // nullable (none): per request the metrics it raises (orh_whatif_run_metrics)
+  const uint32_t* met_ptr;
+  const orh_whatif_metric* mets;
+  uint32_t *d_dist, *d_nh, *d_info;
+};
+
+// a raise resolved to a record: a cut and an entry of the request's sorted
+// (record, raised weight) list
 struct StagedRaise {
   uint32_t rec, w, tail, head, old;  // record, raised weight, its ends, its own weight
 };
+struct StagedRaises {
+  std::vector<uint32_t> ptr;  // [n_req + 1] when the batch has a metric list
+  std::vector<StagedRaise> list;
+  bool any() const { return !list.empty(); }  // else: exactly the run without the lists
+};
 
-int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const uint32_t* ign_ptr,
-               const uint32_t* ign_links, const uint32_t* drn_ptr, const uint32_t* drn_nodes,
-               const uint32_t* met_ptr, const orh_whatif_metric* mets, uint32_t* d_dist, uint32_t* d_nh,
-               uint32_t* d_info) {
+// the staging's pinned host words and device copy for `words` words, after
+// the slot's last upload: need + 25 %, at least 4,096 words
+int stage_acquire(orh_ctx* ctx, StageBuf* b, size_t words) {
+  if (b->ev) ORH_HIP(ctx, hipEventSynchronize(b->ev));  // its last upload is done
+  if (words > b->cap) {
+    if (b->h) hipHostFree(b->h);
+    hipFree(b->d);
+    b->h = nullptr;
+    b->d = nullptr;
+    b->cap = 0;
+    const size_t cap = std::max<size_t>(words + words / 4, 4096);
+    ORH_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&b->h), cap * 4, hipHostMallocDefault));
+    ORH_HIP(ctx, hipMalloc(&b->d, cap * 4));
+    b->cap = cap;
+  }
+  if (!b->ev) ORH_HIP(ctx, hipEventCreateWithFlags(&b->ev, hipEventDisableTiming));
+  return ORH_OK;
+}
+
+// the bytes [lo, hi) that the rows of n_req requests cover
+struct Span {
+  uintptr_t lo, hi;
+};
+Span out_span(const uint32_t* d_dist, const uint32_t* d_nh, uint32_t n_req, uint32_t N) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(d_dist), b = reinterpret_cast<uintptr_t>(d_nh);
+  return {std::min(a, b), std::max(a, b) + size_t{n_req} * N * 4};
+}
+
+// every pending run whose rows overlap the span, and slot also_slot's (-1:
+// none) whatever it wrote, joins the context stream
+int join_overlapping(orh_whatif* job, Span s, int also_slot) {
+  orh_ctx* ctx = job->g->ctx;
+  for (int k = 0; k < kRunSlots; ++k) {
+    RunSlot& r = job->run[k];
+    if (r.pending && (k == also_slot || (s.lo < r.out_hi && r.out_lo < s.hi))) {
+      ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, r.side_ev, 0));
+      r.pending = false;
+    }
+  }
+  return ORH_OK;
+}
+int join_all(orh_whatif* job) { return join_overlapping(job, Span{0, ~uintptr_t{0}}, -1); }
+
+// Source indices and metric raises, validated and resolved before anything is
+// queued: per request its effective raises sorted by record, the largest of a
+// repeated (link, end) kept. A hop-count job checks them and stages none
+int resolve_raises(orh_whatif* job, const WhatifRequests& rq, StagedRaises* out) {
   orh_graph* g = job->g;
   orh_ctx* ctx = g->ctx;
-  const uint32_t N = g->n_nodes, m = static_cast<uint32_t>(job->srcs.size());
+  const uint32_t n_req = rq.n_req, m = static_cast<uint32_t>(job->srcs.size());
   for (uint32_t i = 0; i < n_req; ++i)
-    if (src_idx[i] >= m) return fail(ctx, ORH_E_INVALID, "orh_whatif_run: source index out of range");
-  // metric raises, validated and resolved before anything is queued: per
-  // request its effective raises sorted by record, the largest of a repeated
-  // (link, end) kept. A hop-count job checks them and stages none
-  std::vector<uint32_t> rse_ptr;
-  std::vector<StagedRaise> rse;
-  if (met_ptr) {
-    const std::vector<uint32_t>& erow = entry_rows(g);
-    rse_ptr.assign(size_t{n_req} + 1, 0u);
-    for (uint32_t i = 0; i < n_req; ++i) {
-      const size_t r0 = rse.size();
-      for (uint32_t k = met_ptr[i]; k < met_ptr[i + 1]; ++k) {
-        const orh_whatif_metric& mr = mets[k];
-        if (mr.link >= g->n_links) continue;  // as ignore sets do
-        const uint32_t ent[2] = {g->link_ent[2 * static_cast<size_t>(mr.link)],
-                                 g->link_ent[2 * static_cast<size_t>(mr.link) + 1]};
-        if (ent[0] == ~0u && ent[1] == ~0u) continue;  // a free slot
-        bool end_ok = mr.from_node == ORH_NO_NODE, down = false;
-        for (uint32_t e : ent)
-          if (e != ~0u) {
-            end_ok |= erow[e] == mr.from_node;
-            down |= (g->meta[e] & ORH_META_DOWN) != 0;
-          }
-        if (!end_ok)
-          return fail(ctx, ORH_E_INVALID, "orh_whatif_run_metrics: from_node is not an end of the link");
-        if (down) continue;  // never on a path, whatever it costs
-        for (uint32_t e : ent) {
-          if (e == ~0u || (mr.from_node != ORH_NO_NODE && erow[e] != mr.from_node)) continue;
-          if (mr.metric < g->w_out[e])
-            return fail(ctx, ORH_E_INVALID,
-                        "orh_whatif_run_metrics: metric below the current one (a decrease is a topology change)");
-          if (mr.metric == g->w_out[e] || !job->use_link_metric) continue;
-          rse.push_back({g->pos[e], mr.metric, erow[e], g->col[e], g->w_out[e]});
+    if (rq.src_idx[i] >= m) return fail(ctx, ORH_E_INVALID, "orh_whatif_run: source index out of range");
+  if (!rq.met_ptr) return ORH_OK;
+  std::vector<StagedRaise>& rse = out->list;
+  const std::vector<uint32_t>& erow = entry_rows(g);
+  out->ptr.assign(size_t{n_req} + 1, 0u);
+  for (uint32_t i = 0; i < n_req; ++i) {
+    const size_t r0 = rse.size();
+    for (uint32_t k = rq.met_ptr[i]; k < rq.met_ptr[i + 1]; ++k) {
+      const orh_whatif_metric& mr = rq.mets[k];
+      if (mr.link >= g->n_links) continue;  // as ignore sets do
+      const uint32_t ent[2] = {g->link_ent[2 * static_cast<size_t>(mr.link)],
+                               g->link_ent[2 * static_cast<size_t>(mr.link) + 1]};
+      if (ent[0] == ~0u && ent[1] == ~0u) continue;  // a free slot
+      bool end_ok = mr.from_node == ORH_NO_NODE, down = false;
+      for (uint32_t e : ent)
+        if (e != ~0u) {
+          end_ok |= erow[e] == mr.from_node;
+          down |= (g->meta[e] & ORH_META_DOWN) != 0;
         }
+      if (!end_ok)
+        return fail(ctx, ORH_E_INVALID, "orh_whatif_run_metrics: from_node is not an end of the link");
+      if (down) continue;  // never on a path, whatever it costs
+      for (uint32_t e : ent) {
+        if (e == ~0u || (mr.from_node != ORH_NO_NODE && erow[e] != mr.from_node)) continue;
+        if (mr.metric < g->w_out[e])
+          return fail(ctx, ORH_E_INVALID,
+                      "orh_whatif_run_metrics: metric below the current one (a decrease is a topology change)");
+        if (mr.metric == g->w_out[e] || !job->use_link_metric) continue;
+        rse.push_back({g->pos[e], mr.metric, erow[e], g->col[e], g->w_out[e]});
       }
-      std::sort(rse.begin() + static_cast<ptrdiff_t>(r0), rse.end(), [](const StagedRaise& x, const StagedRaise& y) {
-        return x.rec != y.rec ? x.rec < y.rec : x.w > y.w;
-      });
-      rse.erase(std::unique(rse.begin() + static_cast<ptrdiff_t>(r0), rse.end(),
-                            [](const StagedRaise& x, const StagedRaise& y) { return x.rec == y.rec; }),
-                rse.end());
-      rse_ptr[i + 1] = static_cast<uint32_t>(rse.size());
     }
-    if (!rse.empty()) {
-      // rows are u32: the job's distance bound (whatif_plan) plus what one
-      // request adds to a path must stay below the unreached mark
-      for (uint32_t i = 0; i < n_req; ++i) {
-        uint64_t add = 0;
-        for (uint32_t k = rse_ptr[i]; k < rse_ptr[i + 1]; ++k) add += rse[k].w - rse[k].old;
-        if (job->bound + add >= 0xFFFFFFFFull)
-          return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_run_metrics: raised distances may exceed 32 bits");
-      }
-      const size_t sb = orh::repair_slot_bytes(N, g->n_recs);
-      if (kRepairSlotBudget / std::max<size_t>(sb, 1) == 0)
-        return fail(ctx, ORH_E_UNSUPPORTED,
-                    "orh_whatif_run_metrics: no repair slot fits this graph, and the full search takes no raises");
-    }
+    std::sort(rse.begin() + static_cast<ptrdiff_t>(r0), rse.end(), [](const StagedRaise& x, const StagedRaise& y) {
+      return x.rec != y.rec ? x.rec < y.rec : x.w > y.w;
+    });
+    rse.erase(std::unique(rse.begin() + static_cast<ptrdiff_t>(r0), rse.end(),
+                          [](const StagedRaise& x, const StagedRaise& y) { return x.rec == y.rec; }),
+              rse.end());
+    out->ptr[i + 1] = static_cast<uint32_t>(rse.size());
   }
-  const bool raises = !rse.empty();  // else: exactly the run without the lists
-  // staging: base_row[n] | srcs[n] | ign_ptr[n+1] | ign[..] | with drains: drn_ptr[n+1] | drn[..] |
-  //          cut_ptr[n+1] | (pad to 16 B) cuts uint4[..]
-  const uint32_t n_ign = ign_ptr[n_req];
-  size_t n_cuts = 0;
-  for (uint32_t k = 0; k < n_ign; ++k) {
-    const uint32_t l = ign_links[k];
-    if (l < g->n_links) n_cuts += (g->link_ent[2 * static_cast<size_t>(l)] != ~0u) + (g->link_ent[2 * static_cast<size_t>(l) + 1] != ~0u);
+  if (rse.empty()) return ORH_OK;
+  // rows are u32: the job's distance bound (whatif_plan) plus what one
+  // request adds to a path must stay below the unreached mark
+  for (uint32_t i = 0; i < n_req; ++i) {
+    uint64_t add = 0;
+    for (uint32_t k = out->ptr[i]; k < out->ptr[i + 1]; ++k) add += rse[k].w - rse[k].old;
+    if (job->bound + add >= 0xFFFFFFFFull)
+      return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_run_metrics: raised distances may exceed 32 bits");
   }
-  // a drained node's out-records are cuts too (an upper bound here: the sets
-  // are deduplicated, and lose the request's source, while they are staged)
-  const uint32_t n_drn = drn_ptr ? drn_ptr[n_req] : 0u;
+  if (repair_slots_for(g->n_nodes, g->n_recs, n_req) == 0)
+    return fail(ctx, ORH_E_UNSUPPORTED,
+                "orh_whatif_run_metrics: no repair slot fits this graph, and the full search takes no raises");
+  return ORH_OK;
+}
+
+// The most cuts the batch stages: two per ignored link, one per out-record of
+// a drained node (an upper bound: the sets are deduplicated, and lose the
+// request's source, while they are staged) and one per raised record
+int count_cuts(orh_whatif* job, const WhatifRequests& rq, const StagedRaises& rs, size_t* n_cuts) {
+  const orh_graph* g = job->g;
+  size_t n = rs.list.size();
+  for (uint32_t k = 0; k < rq.ign_ptr[rq.n_req]; ++k) {
+    const size_t l = rq.ign_links[k];
+    if (l < g->n_links) n += (g->link_ent[2 * l] != ~0u) + (g->link_ent[2 * l + 1] != ~0u);
+  }
+  const uint32_t n_drn = rq.drn_ptr ? rq.drn_ptr[rq.n_req] : 0u;
   for (uint32_t k = 0; k < n_drn; ++k) {
-    const uint32_t x = drn_nodes[k];
-    if (x >= N) return fail(ctx, ORH_E_INVALID, "orh_whatif_run_drains: drained node out of range");
-    n_cuts += g->row_ptr[x + 1] - g->row_ptr[x];
+    const uint32_t x = rq.drn_nodes[k];
+    if (x >= g->n_nodes) return fail(g->ctx, ORH_E_INVALID, "orh_whatif_run_drains: drained node out of range");
+    n += g->row_ptr[x + 1] - g->row_ptr[x];
   }
-  n_cuts += rse.size();  // one cut per raised record
-  const size_t off_src = n_req, off_ip = 2 * size_t{n_req}, off_ign = off_ip + n_req + 1;
-  const size_t off_dp = off_ign + n_ign, off_drn = off_dp + n_req + 1;
-  const size_t off_cp = drn_ptr ? off_drn + n_drn : off_ign + n_ign;
-  const size_t off_cuts = (off_cp + n_req + 1 + 3) & ~size_t{3};
-  // with raises, behind the cuts: rse_ptr[n+1] | (pad to 8 B) rse uint2[..]
-  const size_t off_rp = off_cuts + 4 * n_cuts;
-  const size_t off_rse = (off_rp + n_req + 1 + 1) & ~size_t{1};
-  const size_t words = (raises ? off_rse + 2 * rse.size() : off_rp) + 4;
-  {
-    // slot `cur` is reused: its previous run's side part must be done (the
-    // context stream waits); so must the other slot's when it writes rows
-    // this run overwrites
-    const int c = job->cur;
-    const uintptr_t lo = std::min(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh));
-    const uintptr_t hi = std::max(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh)) +
-                         size_t{n_req} * N * 4;
-    for (int k = 0; k < kRunSlots; ++k)
-      if (job->pending[k] && (k == c || (lo < job->out_hi[k] && job->out_lo[k] < hi))) {
-        ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, job->side_ev[k], 0));
-        job->pending[k] = false;
-      }
-  }
-  uint32_t *h = nullptr, *d = nullptr;
-  int rc = whatif_stage(job, words, &h, &d);
-  if (rc) return rc;
-  std::memcpy(h, src_idx, n_req * 4ull);
-  for (uint32_t i = 0; i < n_req; ++i) h[off_src + i] = job->srcs[src_idx[i]];
-  uint32_t* hp = h + off_ip;
-  uint32_t* hi = h + off_ign;
-  uint32_t* hc = h + off_cp;
-  uint4* cuts = reinterpret_cast<uint4*>(h + off_cuts);
+  *n_cuts = n;
+  return ORH_OK;
+}
+
+// The staged words of a run, as u32 offsets; the only place that knows them:
+//   base_row[n] | srcs[n] | ign_ptr[n+1] | ign[n_ign] |
+//   with drains: drn_ptr[n+1] | drn[n_drn] |
+//   cut_ptr[n+1] | (pad to 16 B) cuts uint4[n_cuts] |
+//   with raises: rse_ptr[n+1] | (pad to 8 B) rse uint2[n_rse] |
+//   4 spare words
+struct WhatifLayout {
+  size_t off_src, off_ip, off_ign, off_dp, off_drn, off_cp, off_cuts, off_rp, off_rse, words;
+};
+WhatifLayout whatif_layout(size_t n, size_t n_ign, bool drains, size_t n_drn, size_t n_cuts, size_t n_rse) {
+  WhatifLayout l{};
+  l.off_src = n;
+  l.off_ip = 2 * n;
+  l.off_ign = l.off_ip + n + 1;
+  l.off_dp = l.off_ign + n_ign;
+  l.off_drn = l.off_dp + n + 1;
+  l.off_cp = drains ? l.off_drn + n_drn : l.off_ign + n_ign;
+  l.off_cuts = (l.off_cp + n + 1 + 3) & ~size_t{3};
+  l.off_rp = l.off_cuts + 4 * n_cuts;
+  l.off_rse = (l.off_rp + n + 1 + 1) & ~size_t{1};
+  l.words = (n_rse ? l.off_rse + 2 * n_rse : l.off_rp) + 4;
+  return l;
+}
+
+// The pinned words of a run: per request its ignore set sorted and unique, its
+// drain set likewise and without its own source, and its cuts: ignored link
+// ends, then drained nodes' out-records, then raised records
+void fill_stage(const orh_whatif* job, const WhatifRequests& rq, const StagedRaises& rs, const WhatifLayout& l,
+                uint32_t* h) {
+  orh_graph* g = job->g;
+  const uint32_t n_req = rq.n_req;
+  std::memcpy(h, rq.src_idx, n_req * 4ull);
+  for (uint32_t i = 0; i < n_req; ++i) h[l.off_src + i] = job->srcs[rq.src_idx[i]];
+  uint32_t* hp = h + l.off_ip;
+  uint32_t* hc = h + l.off_cp;
+  uint4* cuts = reinterpret_cast<uint4*>(h + l.off_cuts);
+  uint2* hr = rs.any() ? reinterpret_cast<uint2*>(h + l.off_rse) : nullptr;
   const std::vector<uint32_t>& erow = entry_rows(g);
   size_t ni = 0, nc = 0, nd = 0;
   hp[0] = 0;
   hc[0] = 0;
-  if (drn_ptr) h[off_dp] = 0;
+  if (rq.drn_ptr) h[l.off_dp] = 0;
   for (uint32_t i = 0; i < n_req; ++i) {
-    uint32_t* set = hi + ni;
+    uint32_t* set = h + l.off_ign + ni;
     size_t len = 0;
-    for (uint32_t k = ign_ptr[i]; k < ign_ptr[i + 1]; ++k) set[len++] = ign_links[k];
+    for (uint32_t k = rq.ign_ptr[i]; k < rq.ign_ptr[i + 1]; ++k) set[len++] = rq.ign_links[k];
     std::sort(set, set + len);  // bsearch on device
     len = static_cast<size_t>(std::unique(set, set + len) - set);
     for (size_t k = 0; k < len; ++k) {
-      const uint32_t l = set[k];
-      if (l >= g->n_links) continue;
+      const uint32_t ln = set[k];
+      if (ln >= g->n_links) continue;
       for (int e2 = 0; e2 < 2; ++e2) {
-        const uint32_t e = g->link_ent[2 * static_cast<size_t>(l) + e2];
+        const uint32_t e = g->link_ent[2 * static_cast<size_t>(ln) + e2];
         if (e == ~0u) continue;
         cuts[nc++] = make_uint4(erow[e], g->col[e], g->pos[e], 0u);
       }
     }
     ni += len;
     hp[i + 1] = static_cast<uint32_t>(ni);
-    if (drn_ptr) {
+    if (rq.drn_ptr) {
       // the request's drain set, sorted (bsearch on device), without its own
       // source (an overloaded source still relaxes, LinkState.cpp:831-838);
       // one cut per out-record of each node: the seeds test their tightness
       // and skip a tail that is overloaded already or unreached
-      uint32_t* dset = h + off_drn + nd;
+      uint32_t* dset = h + l.off_drn + nd;
       size_t dl = 0;
-      for (uint32_t k = drn_ptr[i]; k < drn_ptr[i + 1]; ++k)
-        if (drn_nodes[k] != job->srcs[src_idx[i]]) dset[dl++] = drn_nodes[k];
+      for (uint32_t k = rq.drn_ptr[i]; k < rq.drn_ptr[i + 1]; ++k)
+        if (rq.drn_nodes[k] != job->srcs[rq.src_idx[i]]) dset[dl++] = rq.drn_nodes[k];
       std::sort(dset, dset + dl);
       dl = static_cast<size_t>(std::unique(dset, dset + dl) - dset);
       for (size_t k = 0; k < dl; ++k) {
@@ -1767,249 +1858,267 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
           if (g->meta[e] != ORH_META_EMPTY) cuts[nc++] = make_uint4(x, g->col[e], g->pos[e], 0u);
       }
       nd += dl;
-      h[off_dp + i + 1] = static_cast<uint32_t>(nd);
+      h[l.off_dp + i + 1] = static_cast<uint32_t>(nd);
     }
-    if (raises) {
-      uint2* hr = reinterpret_cast<uint2*>(h + off_rse);
-      for (uint32_t k = rse_ptr[i]; k < rse_ptr[i + 1]; ++k) {
-        cuts[nc++] = make_uint4(rse[k].tail, rse[k].head, rse[k].rec, 0u);
-        hr[k] = make_uint2(rse[k].rec, rse[k].w);
+    if (rs.any())
+      for (uint32_t k = rs.ptr[i]; k < rs.ptr[i + 1]; ++k) {
+        cuts[nc++] = make_uint4(rs.list[k].tail, rs.list[k].head, rs.list[k].rec, 0u);
+        hr[k] = make_uint2(rs.list[k].rec, rs.list[k].w);
       }
-    }
     hc[i + 1] = static_cast<uint32_t>(nc);
   }
-  if (raises) std::memcpy(h + off_rp, rse_ptr.data(), (size_t{n_req} + 1) * 4);
-  const int c = job->cur;
-  job->cur = (job->cur + 1) % kRunSlots;
-  ORH_HIP(ctx, hipMemcpyAsync(d, h, words * 4, hipMemcpyHostToDevice, ctx->stream));
-  ORH_HIP(ctx, hipEventRecord(job->stage_ev[c], ctx->stream));
+  if (rs.any()) std::memcpy(h + l.off_rp, rs.ptr.data(), (size_t{n_req} + 1) * 4);
+}
 
+// what provision_run decided for a run
+struct RunPlan {
+  uint32_t n_slots;  // workgroups of the slot tier; 0: no slot fits the budget
+  size_t slot_bytes;
+  uint8_t* slot_mem;
+  // full searches wanted for the slot tier's queue: ORH_WHATIF_FULL=n (A/B),
+  // or the job's ORH_WHATIF_SEARCH_LARGE (ORH_WHATIF_SEARCH_CAP per run). A
+  // run with raises takes none (the search knows no raised weights): its slot
+  // tier ends every request
+  uint32_t full_n;
+  bool split;           // the slot tier on its own stream, over the run slot's memory
+  uint32_t full_cap;    // of full_n, what the labels' 1 GB and the batch allow
+  uint32_t skip_large;  // no tier 2 in front of the full searches
+  // rows the full search may take, i.e. the labels it needs: full_cap of the
+  // slot tier's queue, or without slots any of the batch (the flagged ones)
+  uint32_t search_rows;
+};
+
+// *p freed and exactly `bytes` allocated in its place; the caller has waited
+// for whatever may still use the old memory
+int regrow(orh_ctx* ctx, void** p, size_t* cap, size_t bytes) {
+  hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  ORH_HIP(ctx, hipMalloc(p, bytes));
+  *cap = bytes;
+  return ORH_OK;
+}
+
+// Work queues, slot memory and full-search labels of the run in slot c, each
+// grown to the exact need, after the wait that makes freeing the old one safe
+int provision_run(orh_whatif* job, int c, uint32_t n_req, bool raises, RunPlan* out) {
+  orh_graph* g = job->g;
+  orh_ctx* ctx = g->ctx;
+  RunSlot& slot = job->run[c];
+  const uint32_t N = g->n_nodes;
+  const WhatifKnobs& knobs = whatif_knobs();
   const size_t work = 3 * size_t{n_req} + orh::kWhatifCounters + n_req;
-  if (work > job->work_cap[c]) {
-    if (job->pending[c]) ORH_HIP(ctx, hipStreamSynchronize(job->side));  // its old buffer may be in use
-    hipFree(job->d_work[c]);
-    job->d_work[c] = nullptr;
-    job->work_cap[c] = 0;
-    ORH_HIP(ctx, hipMalloc(&job->d_work[c], work * 4));
-    job->work_cap[c] = work;
+  if (work * 4 > slot.work_cap) {
+    if (slot.pending) ORH_HIP(ctx, hipStreamSynchronize(job->side));  // its old buffer may be in use
+    const int rc = regrow(ctx, reinterpret_cast<void**>(&slot.d_work), &slot.work_cap, work * 4);
+    if (rc) return rc;
   }
-  uint32_t* counters = job->d_work[c] + 3 * size_t{n_req};
-  uint32_t* flags = counters + orh::kWhatifCounters;
-  ORH_HIP(ctx, hipMemsetAsync(counters, 0, (orh::kWhatifCounters + n_req) * 4ull, ctx->stream));
-  const size_t slot_bytes = orh::repair_slot_bytes(N, g->n_recs);
-  const uint32_t n_slots = static_cast<uint32_t>(std::min<size_t>(
-      std::min<size_t>(kRepairSlots, n_req), kRepairSlotBudget / std::max<size_t>(slot_bytes, 1)));
-  uint8_t* slot_mem = nullptr;
-  static const uint32_t full_env = [] {
-    const char* e = getenv("ORH_WHATIF_FULL");
-    return e ? static_cast<uint32_t>(atoi(e)) : 0u;
-  }();
-  static const bool t3_split = [] {  // ORH_WHATIF_T3_SPLIT=0: the slot tier stays on `side` (A/B)
-    const char* e = getenv("ORH_WHATIF_T3_SPLIT");
-    return !(e && atoi(e) == 0);
-  }();
-  // full searches for the slot tier's queue: ORH_WHATIF_FULL=n (A/B), or the
-  // job's ORH_WHATIF_SEARCH_LARGE (16 per run)
-  static const uint32_t large_cap = [] {  // ORH_WHATIF_SEARCH_CAP (A/B): the flag's searches per run
-    const char* e = getenv("ORH_WHATIF_SEARCH_CAP");
-    // 256: tier 1's whole overflow of a C4 block (profiles/r06/an_skip_t2_ab/);
-    // 8 / 16 / 32 behind tier 2: profiles/r06/ab_search_cap.txt
-    return e && atoi(e) > 0 ? static_cast<uint32_t>(atoi(e)) : 256u;
-  }();
-  // a run with raises takes no full search (the search knows no raised
-  // weights): its slot tier ends every request
-  const uint32_t full_n = raises ? 0u
-                          : full_env ? full_env
-                          : (job->flags & ORH_WHATIF_SEARCH_LARGE) ? large_cap
-                                                                    : 0u;
-  const bool split = n_slots && full_n == 0 && t3_split;
-  if (split) {
-    // run slot c's own slot memory, grown only with its stream idle
-    if (n_slots * slot_bytes > job->t3_slots_cap[c]) {
+  ORH_HIP(ctx, hipMemsetAsync(slot.d_work + 3 * size_t{n_req}, 0, (orh::kWhatifCounters + n_req) * 4ull,
+                              ctx->stream));
+  RunPlan p{};
+  p.slot_bytes = orh::repair_slot_bytes(N, g->n_recs);
+  p.n_slots = repair_slots_for(N, g->n_recs, n_req);
+  p.full_n = raises ? 0u : knobs.full ? knobs.full : (job->flags & ORH_WHATIF_SEARCH_LARGE) ? knobs.search_cap : 0u;
+  p.split = p.n_slots && p.full_n == 0 && knobs.t3_split;
+  const size_t slots_bytes = p.n_slots * p.slot_bytes;
+  if (p.split) {
+    // run slot c's own slot memory, grown only with its streams idle
+    if (slots_bytes > slot.t3_slots_cap) {
       for (hipStream_t t : job->t3) ORH_HIP(ctx, hipStreamSynchronize(t));
-      hipFree(job->t3_slots[c]);
-      job->t3_slots[c] = nullptr;
-      job->t3_slots_cap[c] = 0;
-      ORH_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&job->t3_slots[c]), n_slots * slot_bytes));
-      job->t3_slots_cap[c] = n_slots * slot_bytes;
+      const int rc = regrow(ctx, reinterpret_cast<void**>(&slot.t3_slots), &slot.t3_slots_cap, slots_bytes);
+      if (rc) return rc;
     }
-    slot_mem = job->t3_slots[c];
-  } else if (n_slots) {
+    p.slot_mem = slot.t3_slots;
+  } else if (p.n_slots) {
     // the context's slots while no other job's side stream may use them,
     // else the job's own; grown only with the side stream idle
     if (!ctx->slots_owner) ctx->slots_owner = job;
     const bool borrowed = ctx->slots_owner == job;
-    uint8_t** p = borrowed ? &ctx->d_rep_slots : &job->own_slots;
+    uint8_t** mem = borrowed ? &ctx->d_rep_slots : &job->own_slots;
     size_t* cap = borrowed ? &ctx->d_rep_slots_cap : &job->own_slots_cap;
-    if (n_slots * slot_bytes > *cap) ORH_HIP(ctx, hipStreamSynchronize(job->side));
-    rc = ensure_bytes(ctx, p, cap, n_slots * slot_bytes);
+    if (slots_bytes > *cap) ORH_HIP(ctx, hipStreamSynchronize(job->side));
+    const int rc = ensure_bytes(ctx, mem, cap, slots_bytes);
     if (rc) return rc;
-    slot_mem = *p;
+    p.slot_mem = *mem;
   }
-  const size_t nbase = static_cast<size_t>(m) * N;
+  if (p.n_slots) {
+    const size_t by_mem = (size_t{1} << 30) / (static_cast<size_t>(N) * 8);
+    p.full_cap = static_cast<uint32_t>(std::min<size_t>({p.full_n, by_mem, n_req}));
+    p.skip_large = (knobs.skip_t2 && p.full_cap) ? 1u : 0u;
+  }
+  // job-owned labels: the searches run on the job's side stream, which later
+  // work on the context stream (searches over ctx->d_labels) does not wait for
+  p.search_rows = p.n_slots ? p.full_cap : n_req;
+  const size_t need = static_cast<size_t>(p.search_rows) * N * 8;
+  if (need > job->full_lab_cap) {
+    ORH_HIP(ctx, hipStreamSynchronize(job->side));  // the old buffer may be in use
+    const int rc = regrow(ctx, &job->d_full_lab, &job->full_lab_cap, need);
+    if (rc) return rc;
+  }
+  *out = p;
+  return ORH_OK;
+}
+
+orh::RepairArgs fill_repair_args(const orh_whatif* job, int c, const WhatifLayout& l, const RunPlan& p,
+                                 const WhatifRequests& rq, bool raises) {
+  const orh_graph* g = job->g;
+  const orh_ctx* ctx = g->ctx;
+  const RunSlot& slot = job->run[c];
+  const uint32_t* d = slot.stage.d;
   orh::RepairArgs ra{};
-  ra.n_nodes = N;
-  ra.n_req = n_req;
+  ra.n_nodes = g->n_nodes;
+  ra.n_req = rq.n_req;
   ra.use_link_metric = job->use_link_metric;
-  repair_caps(ctx, N, &ra.cap_a, &ra.cap_e);
+  repair_caps(ctx, g->n_nodes, &ra.cap_a, &ra.cap_e);
   ra.recs = g->d_recs;
   ra.link = g->d_link;
   ra.rank_out = g->d_rank_out;
   ra.rev = g->d_rev;
   ra.ovl = g->d_ovl;
   ra.base_dist = job->d_base;
-  ra.base_nh = job->d_base + nbase;
+  ra.base_nh = job->d_base + job->srcs.size() * static_cast<size_t>(g->n_nodes);
   ra.base_row = d;
-  ra.srcs = d + off_src;
-  ra.ign_ptr = d + off_ip;
-  ra.ign = d + off_ign;
-  if (drn_ptr) {
-    ra.drn_ptr = d + off_dp;
-    ra.drn = d + off_drn;
+  ra.srcs = d + l.off_src;
+  ra.ign_ptr = d + l.off_ip;
+  ra.ign = d + l.off_ign;
+  if (rq.drn_ptr) {
+    ra.drn_ptr = d + l.off_dp;
+    ra.drn = d + l.off_drn;
   }
   if (raises) {
-    ra.rse_ptr = d + off_rp;
-    ra.rse = reinterpret_cast<const uint2*>(d + off_rse);
+    ra.rse_ptr = d + l.off_rp;
+    ra.rse = reinterpret_cast<const uint2*>(d + l.off_rse);
   }
-  ra.cut_ptr = d + off_cp;
-  ra.cuts = reinterpret_cast<const uint4*>(d + off_cuts);
-  ra.out_dist = d_dist;
-  ra.out_nh = d_nh;
-  ra.fallback = flags;
-  ra.info = d_info;
-  ra.queues = job->d_work[c];
-  ra.counters = counters;
-  ra.slot_mem = slot_mem;
-  ra.slot_bytes = slot_bytes;
-  ra.n_slots = n_slots;
+  ra.cut_ptr = d + l.off_cp;
+  ra.cuts = reinterpret_cast<const uint4*>(d + l.off_cuts);
+  ra.out_dist = rq.d_dist;
+  ra.out_nh = rq.d_nh;
+  ra.queues = slot.d_work;
+  ra.counters = slot.d_work + 3 * size_t{rq.n_req};
+  ra.fallback = ra.counters + orh::kWhatifCounters;
+  ra.info = rq.d_info;
+  ra.slot_mem = p.slot_mem;
+  ra.slot_bytes = p.slot_bytes;
+  ra.n_slots = p.n_slots;
   ra.n_recs = g->n_recs;
   ra.n_cu = ctx->n_cu;
   ra.share_base = (job->flags & ORH_WHATIF_SHARE_BASE) ? 1u : 0u;
-  // ORH_WHATIF_FULL=n (A/B, default 0): the slot tier's queue goes to full
-  // searches first, up to n rows (labels within 1 GB). C4: 79 requests per
-  // job searched in full 30.7-31.2 ms against 29.6 ms in slots
-  // (profiles/r03/r_c4_full_search_ab.txt): the slots stay the default
-  if (n_slots) {
-    const size_t by_mem = (size_t{1} << 30) / (static_cast<size_t>(N) * 8);
-    ra.full_cap = static_cast<uint32_t>(std::min<size_t>({full_n, by_mem, n_req}));
-    // with full searches, tier 1's overflow goes to them directly: tier 2
-    // between them put its 0.4 ms on a short job's critical path (C4 block of
-    // 8: 5.34 -> 4.73 ms, profiles/r06/an_skip_t2_ab/); ORH_WHATIF_SKIP_T2=0
-    // keeps tier 2 (A/B)
-    static const bool skip_t2 = [] {
-      const char* e = getenv("ORH_WHATIF_SKIP_T2");
-      return !(e && atoi(e) == 0);
-    }();
-    ra.skip_large = (skip_t2 && ra.full_cap) ? 1u : 0u;
-    if (ra.full_cap) {
-      const size_t need = static_cast<size_t>(ra.full_cap) * N * 8;
-      if (need > job->full_lab_cap) {
-        ORH_HIP(ctx, hipStreamSynchronize(job->side));  // the old buffer may be in use
-        hipFree(job->d_full_lab);
-        job->d_full_lab = nullptr;
-        job->full_lab_cap = 0;
-        ORH_HIP(ctx, hipMalloc(&job->d_full_lab, need));
-        job->full_lab_cap = need;
-      }
-    }
+  ra.full_cap = p.full_cap;
+  ra.skip_large = p.skip_large;
+  return ra;
+}
+
+// The full search (spf_global_nh_async_kernel) over the run's staged requests.
+// With slots it takes the first entries of the slot tier's queue: workgroup b
+// searches request queue[b] while b < the queue's length. Without, the
+// requests that outgrew tier 2, through the fallback flags as its row mask
+// (the others exit at once; scratch is unused, every row is < n_out)
+orh::SpfArgs full_search_args(const orh_whatif* job, const orh::RepairArgs& ra) {
+  const orh_graph* g = job->g;
+  orh::SpfArgs a{};
+  a.n_nodes = ra.n_nodes;
+  a.n_out = ra.n_req;
+  a.recs = g->d_recs;
+  a.link = g->d_link;
+  a.srcs = ra.srcs;
+  a.ignore_ptr = ra.ign_ptr;
+  a.ignore_links = ra.ign;
+  a.use_link_metric = job->use_link_metric;
+  a.w0 = job->use_link_metric ? g->max_out : 1u;
+  a.delta = job->uniform ? a.w0
+                         : std::max<uint32_t>(1u, static_cast<uint32_t>(static_cast<uint64_t>(g->mean_out) *
+                                                                        g->ctx->delta_pct / 100u));
+  a.out_dist = ra.out_dist;
+  a.scratch = g->ctx->d_scratch;
+  a.labels = static_cast<unsigned long long*>(job->d_full_lab);
+  a.out_nh = ra.out_nh;
+  a.words = 1;
+  a.rank_out = g->d_rank_out;
+  a.drain_ptr = ra.drn_ptr;
+  a.drain_nodes = ra.drn;
+  if (ra.n_slots) {
+    const uint32_t q = orh::repair_slot_queue(ra);
+    a.row_list = ra.queues + static_cast<size_t>(q) * ra.n_req;
+    a.row_count = ra.counters + 2 * q;
+  } else {
+    a.row_mask = ra.fallback;
   }
+  return a;
+}
+
+// Seed and copy on the context stream; the repair tiers on `side` behind
+// them, the slot tier of a split run on its t3 stream; then the full search
+// on `side`. side_ev marks the end of the run's side part
+int launch_run(orh_whatif* job, int c, const orh::RepairArgs& ra, const RunPlan& p) {
+  orh_graph* g = job->g;
+  orh_ctx* ctx = g->ctx;
+  RunSlot& slot = job->run[c];
   hipError_t e = orh::launch_repair_front(ra, g->ell_k, ctx->lds_limit, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "what-if repair launch");
-  ORH_HIP(ctx, hipEventRecord(job->front_ev[c], ctx->stream));
+  ORH_HIP(ctx, hipEventRecord(slot.front_ev, ctx->stream));
   // the large repairs on the side stream, after this run's front part; the
   // previous side part is ordered before them on that stream
-  ORH_HIP(ctx, hipStreamWaitEvent(job->side, job->front_ev[c], 0));
+  ORH_HIP(ctx, hipStreamWaitEvent(job->side, slot.front_ev, 0));
   hipStream_t t3s = job->t3[job->runs % orh_whatif::kT3];
   ++job->runs;
-  e = split ? orh::launch_repair_back_split(ra, g->ell_k, ctx->lds_limit, job->side, t3s, job->mid_ev[c])
-            : orh::launch_repair_back(ra, g->ell_k, ctx->lds_limit, job->side);
+  e = p.split ? orh::launch_repair_back_split(ra, g->ell_k, ctx->lds_limit, job->side, t3s, slot.mid_ev)
+              : orh::launch_repair_back(ra, g->ell_k, ctx->lds_limit, job->side);
   if (e != hipSuccess) return hip_fail(ctx, e, "what-if repair launch (large tiers)");
-  if (n_slots && ra.full_cap) {
-    // workgroup b searches request queue[b] while b < the queue's length
-    const uint32_t q = orh::repair_slot_queue(ra);
-    orh::SpfPlan fp = orh::plan_spf(N, job->uniform, job->bound, g->ell_k, ctx->lds_limit, false,
+  if (p.search_rows) {
+    orh::SpfPlan fp = orh::plan_spf(ra.n_nodes, job->uniform, job->bound, g->ell_k, ctx->lds_limit, false,
                                     orh::SpfMode::kGlobal);
     if (fp.variant == orh::SpfVariant::kUnsupported)
       return fail(ctx, ORH_E_UNSUPPORTED, "what-if: no search plan for this graph");
     fp.variant = orh::SpfVariant::kGlobalNh;
     fp.block = 1024;
-    orh::SpfArgs a{};
-    a.n_nodes = N;
-    a.n_out = n_req;
-    a.recs = g->d_recs;
-    a.link = g->d_link;
-    a.srcs = ra.srcs;
-    a.ignore_ptr = ra.ign_ptr;
-    a.ignore_links = ra.ign;
-    a.use_link_metric = job->use_link_metric;
-    a.w0 = job->use_link_metric ? g->max_out : 1u;
-    a.delta = job->uniform ? a.w0
-                           : std::max<uint32_t>(1u, static_cast<uint32_t>(
-                                                        static_cast<uint64_t>(g->mean_out) * ctx->delta_pct / 100u));
-    a.out_dist = d_dist;
-    a.scratch = ctx->d_scratch;
-    a.labels = static_cast<unsigned long long*>(job->d_full_lab);
-    a.out_nh = d_nh;
-    a.words = 1;
-    a.rank_out = g->d_rank_out;
-    a.drain_ptr = ra.drn_ptr;
-    a.drain_nodes = ra.drn;
-    a.row_list = ra.queues + static_cast<size_t>(q) * n_req;
-    a.row_count = ra.counters + 2 * q;
-    e = orh::launch_spf(fp, a, ra.full_cap, job->side);
-    if (e != hipSuccess) return hip_fail(ctx, e, "what-if full-search launch");
+    e = orh::launch_spf(fp, full_search_args(job, ra), p.search_rows, job->side);
+    if (e != hipSuccess)
+      return hip_fail(ctx, e, p.n_slots ? "what-if full-search launch" : "what-if fallback launch");
   }
-  if (n_slots == 0) {
-    // no slot fits the budget: the requests that outgrew tier 2 are searched
-    // in full (spf_global_nh_async_kernel with the flags as its row mask)
-    orh::SpfPlan fp = orh::plan_spf(N, job->uniform, job->bound, g->ell_k, ctx->lds_limit, false,
-                                    orh::SpfMode::kGlobal);
-    fp.variant = orh::SpfVariant::kGlobalNh;
-    fp.block = 1024;  // only the flagged rows search; the rest exit at once
-    // job-owned labels: this search runs on the job's side stream, which
-    // later work on the context stream (searches over ctx->d_labels) does
-    // not wait for
-    const size_t need = static_cast<size_t>(n_req) * N * 8;
-    if (need > job->full_lab_cap) {
-      ORH_HIP(ctx, hipStreamSynchronize(job->side));  // the old buffer may be in use
-      hipFree(job->d_full_lab);
-      job->d_full_lab = nullptr;
-      job->full_lab_cap = 0;
-      ORH_HIP(ctx, hipMalloc(&job->d_full_lab, need));
-      job->full_lab_cap = need;
-    }
-    orh::SpfArgs a{};
-    a.n_nodes = N;
-    a.n_out = n_req;
-    a.recs = g->d_recs;
-    a.link = g->d_link;
-    a.srcs = ra.srcs;
-    a.ignore_ptr = ra.ign_ptr;
-    a.ignore_links = ra.ign;
-    a.use_link_metric = job->use_link_metric;
-    a.w0 = job->use_link_metric ? g->max_out : 1u;
-    a.delta = job->uniform ? a.w0
-                           : std::max<uint32_t>(1u, static_cast<uint32_t>(
-                                                        static_cast<uint64_t>(g->mean_out) * ctx->delta_pct / 100u));
-    a.out_dist = d_dist;
-    a.scratch = ctx->d_scratch;  // unused: every row is < n_out
-    a.labels = static_cast<unsigned long long*>(job->d_full_lab);
-    a.out_nh = d_nh;
-    a.words = 1;
-    a.rank_out = g->d_rank_out;
-    a.drain_ptr = ra.drn_ptr;
-    a.drain_nodes = ra.drn;
-    a.row_mask = flags;
-    e = orh::launch_spf(fp, a, n_req, job->side);
-    if (e != hipSuccess) return hip_fail(ctx, e, "what-if fallback launch");
-  }
-  // the run's side part ends with its slot tier (t3[c], ordered after tiers
-  // 1 and 2 through mid_ev[c]) or on `side`
-  ORH_HIP(ctx, hipEventRecord(job->side_ev[c], split ? t3s : job->side));
-  job->pending[c] = true;
-  job->out_lo[c] = std::min(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh));
-  job->out_hi[c] = std::max(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh)) +
-                   size_t{n_req} * N * 4;
+  // the run's side part ends with its slot tier (its t3 stream, ordered after
+  // tiers 1 and 2 through mid_ev) or on `side`
+  ORH_HIP(ctx, hipEventRecord(slot.side_ev, p.split ? t3s : job->side));
+  return ORH_OK;
+}
+
+// one batch of requests of a job: seed and copy and the small repair tiers
+// on the context stream; the large tiers, the slot tier (t3 streams) and,
+// without slots, the full search for what outgrew tier 2 on the job's side
+// streams, over job-owned memory (slots, labels), joined back into the
+// context stream through side_ev
+int whatif_run(orh_whatif* job, const WhatifRequests& rq) {
+  orh_graph* g = job->g;
+  orh_ctx* ctx = g->ctx;
+  const uint32_t n_req = rq.n_req;
+  StagedRaises rs;
+  size_t n_cuts = 0;
+  int rc = resolve_raises(job, rq, &rs);
+  if (!rc) rc = count_cuts(job, rq, rs, &n_cuts);
+  if (rc) return rc;
+  const WhatifLayout lay = whatif_layout(n_req, rq.ign_ptr[n_req], rq.drn_ptr != nullptr,
+                                         rq.drn_ptr ? rq.drn_ptr[n_req] : 0u, n_cuts, rs.list.size());
+  // slot `cur` is reused: its previous run's side part must be done (the
+  // context stream waits); so must the other slots' when they write rows this
+  // run overwrites
+  const int c = job->cur;
+  RunSlot& slot = job->run[c];
+  const Span out = out_span(rq.d_dist, rq.d_nh, n_req, g->n_nodes);
+  rc = join_overlapping(job, out, c);
+  if (!rc) rc = stage_acquire(ctx, &slot.stage, lay.words);
+  if (rc) return rc;
+  fill_stage(job, rq, rs, lay, slot.stage.h);
+  job->cur = (c + 1) % kRunSlots;
+  ORH_HIP(ctx, hipMemcpyAsync(slot.stage.d, slot.stage.h, lay.words * 4, hipMemcpyHostToDevice, ctx->stream));
+  ORH_HIP(ctx, hipEventRecord(slot.stage.ev, ctx->stream));
+  RunPlan plan{};
+  rc = provision_run(job, c, n_req, rs.any(), &plan);
+  if (rc) return rc;
+  const orh::RepairArgs ra = fill_repair_args(job, c, lay, plan, rq, rs.any());
+  rc = launch_run(job, c, ra, plan);
+  if (rc) return rc;
+  slot.pending = true;
+  slot.out_lo = out.lo;
+  slot.out_hi = out.hi;
   job->requests += n_req;
   ctx->counters.spf_runs += n_req;  // one runSpf per request (LinkState.cpp:815)
   ctx->counters.spf_launches += 1;
@@ -2021,11 +2130,8 @@ int whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const u
 // queued on it afterwards sees all of the job's rows
 int whatif_flush(orh_whatif* job) {
   orh_ctx* ctx = job->g->ctx;
-  for (int c = 0; c < kRunSlots; ++c)
-    if (job->pending[c]) {
-      ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, job->side_ev[c], 0));
-      job->pending[c] = false;
-    }
+  const int rc = join_all(job);
+  if (rc) return rc;
   ORH_HIP(ctx, hipEventRecord(job->ev_end, ctx->stream));
   return ORH_OK;
 }
@@ -2043,53 +2149,32 @@ int whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, cons
   const bool share = (job->flags & ORH_WHATIF_SHARE_BASE) != 0;
   if (share && !d_info)
     return fail(ctx, ORH_E_INVALID, "orh_whatif_impact: a SHARE_BASE job's tier-0 rows were never written, d_info is needed");
-  // a graph whose runs have no tier-3 slots (whatif_run's n_slots == 0) leaves
-  // tier 0 in d_info for the requests its full search re-derived: tier 0 does
-  // not prove there that the row stands, so every row is scanned
-  if (kRepairSlotBudget / std::max<size_t>(orh::repair_slot_bytes(N, g->n_recs), 1) == 0) {
+  // a graph whose runs have no tier-3 slots leaves tier 0 in d_info for the
+  // requests its full search re-derived: tier 0 does not prove there that the
+  // row stands, so every row is scanned
+  if (repair_slots_for(N, g->n_recs, n_req) == 0) {
     if (share) return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_impact: SHARE_BASE on a graph without repair slots");
     d_info = nullptr;
   }
   // every pending run whose rows overlap the given ones joins the context stream
-  {
-    const uintptr_t lo = std::min(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh));
-    const uintptr_t hi = std::max(reinterpret_cast<uintptr_t>(d_dist), reinterpret_cast<uintptr_t>(d_nh)) +
-                         size_t{n_req} * N * 4;
-    for (int k = 0; k < kRunSlots; ++k)
-      if (job->pending[k] && lo < job->out_hi[k] && job->out_lo[k] < hi) {
-        ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, job->side_ev[k], 0));
-        job->pending[k] = false;
-      }
-  }
-  const int c = job->imp_cur;
+  int rc = join_overlapping(job, out_span(d_dist, d_nh, n_req, N), -1);
+  if (rc) return rc;
+  StageBuf& st = job->imp[job->imp_cur];
   const size_t words = 2 * size_t{n_req};
-  if (job->imp_ev[c]) ORH_HIP(ctx, hipEventSynchronize(job->imp_ev[c]));  // its last upload is done
-  if (words > job->imp_cap[c]) {
-    if (job->h_imp[c]) hipHostFree(job->h_imp[c]);
-    hipFree(job->d_imp[c]);
-    job->h_imp[c] = nullptr;
-    job->d_imp[c] = nullptr;
-    job->imp_cap[c] = 0;
-    const size_t cap = std::max<size_t>(words + words / 4, 4096);
-    ORH_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&job->h_imp[c]), cap * 4, hipHostMallocDefault));
-    ORH_HIP(ctx, hipMalloc(&job->d_imp[c], cap * 4));
-    job->imp_cap[c] = cap;
-  }
-  if (!job->imp_ev[c]) ORH_HIP(ctx, hipEventCreateWithFlags(&job->imp_ev[c], hipEventDisableTiming));
-  uint32_t* h = job->h_imp[c];
-  uint32_t* d = job->d_imp[c];
-  std::memcpy(h, src_idx, n_req * 4ull);
-  for (uint32_t i = 0; i < n_req; ++i) h[n_req + i] = job->srcs[src_idx[i]];
-  job->imp_cur = (c + 1) % kRunSlots;
-  ORH_HIP(ctx, hipMemcpyAsync(d, h, words * 4, hipMemcpyHostToDevice, ctx->stream));
-  ORH_HIP(ctx, hipEventRecord(job->imp_ev[c], ctx->stream));
+  rc = stage_acquire(ctx, &st, words);
+  if (rc) return rc;
+  std::memcpy(st.h, src_idx, n_req * 4ull);
+  for (uint32_t i = 0; i < n_req; ++i) st.h[n_req + i] = job->srcs[src_idx[i]];
+  job->imp_cur = (job->imp_cur + 1) % kRunSlots;
+  ORH_HIP(ctx, hipMemcpyAsync(st.d, st.h, words * 4, hipMemcpyHostToDevice, ctx->stream));
+  ORH_HIP(ctx, hipEventRecord(st.ev, ctx->stream));
   orh::ImpactArgs a{};
   a.n_nodes = N;
   a.n_req = n_req;
   a.base_dist = job->d_base;
   a.base_nh = job->d_base + static_cast<size_t>(m) * N;
-  a.base_row = d;
-  a.srcs = d + n_req;
+  a.base_row = st.d;
+  a.srcs = st.d + n_req;
   a.dist = d_dist;
   a.nh = d_nh;
   a.info = d_info;
@@ -2103,6 +2188,7 @@ int whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, cons
   if (e != hipSuccess) return hip_fail(ctx, e, "what-if impact launch");
   return ORH_OK;
 }
+
 
 // the plain SPFs of the job's sources into its base rows, on the graph as it
 // is now (create, and orh_whatif_refresh after topology changes); the side
@@ -2121,12 +2207,8 @@ int whatif_base(orh_whatif* job) {
   job->uniform = uniform;
   job->bound = bound;
   rc = ensure_rev(g);
+  if (!rc) rc = join_all(job);
   if (rc) return rc;
-  for (int c = 0; c < kRunSlots; ++c)
-    if (job->pending[c]) {
-      ORH_HIP(ctx, hipStreamWaitEvent(ctx->stream, job->side_ev[c], 0));
-      job->pending[c] = false;
-    }
   const uint32_t m = static_cast<uint32_t>(job->srcs.size());
   const size_t nd = static_cast<size_t>(std::max<uint32_t>(m, 1)) * g->n_nodes;
   if (nd * 8 > job->base_cap) {
@@ -2182,10 +2264,10 @@ int whatif_create(orh_graph* g, const uint32_t* h_srcs, uint32_t n_srcs, int32_t
   if (hipEventCreate(&job->ev_begin) != hipSuccess || hipEventCreate(&job->ev_end) != hipSuccess ||
       hipStreamCreateWithFlags(&job->side, hipStreamNonBlocking) != hipSuccess)
     return bail(fail(ctx, ORH_E_DEVICE, "orh_whatif_create: events / stream"));
-  for (int c = 0; c < kRunSlots; ++c)
-    if (hipEventCreateWithFlags(&job->front_ev[c], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&job->side_ev[c], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&job->mid_ev[c], hipEventDisableTiming) != hipSuccess)
+  for (RunSlot& r : job->run)
+    if (hipEventCreateWithFlags(&r.front_ev, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&r.side_ev, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&r.mid_ev, hipEventDisableTiming) != hipSuccess)
       return bail(fail(ctx, ORH_E_DEVICE, "orh_whatif_create: events"));
   for (hipStream_t& t : job->t3)
     if (hipStreamCreateWithFlags(&t, hipStreamNonBlocking) != hipSuccess)
@@ -2218,9 +2300,8 @@ int run_repair(orh_graph* g, const orh_spf_request* req, uint32_t* d_dist, uint3
   int rc = whatif_create(g, base_srcs.data(), static_cast<uint32_t>(base_srcs.size()), req->use_link_metric, &job);
   if (rc) return rc;
   ORH_HIP(ctx, hipEventRecord(ctx->evm, ctx->stream));
-  rc = whatif_run(job, n_src, base_row.data(), req->h_ignore_ptr, req->h_ignore_links, nullptr, nullptr, nullptr,
-                  nullptr, d_dist,
-                  d_nh, nullptr);
+  rc = whatif_run(job, WhatifRequests{n_src, base_row.data(), req->h_ignore_ptr, req->h_ignore_links, nullptr, nullptr,
+                                      nullptr, nullptr, d_dist, d_nh, nullptr});
   if (!rc) rc = whatif_flush(job);
   if (rc) {
     orh_whatif_destroy(job);
@@ -2249,56 +2330,48 @@ int orh_whatif_create(orh_graph* g, const uint32_t* h_srcs, uint32_t n_srcs, int
   return whatif_create(g, h_srcs, n_srcs, use_link_metric, out);
 }
 
-int orh_whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
-                   const uint32_t* h_ignore_links, uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info) {
+// the checks the orh_whatif_run* entry points share, under `fn`'s name, then
+// the run; a list that an entry point does not take is null here
+static int checked_run(orh_whatif* job, const WhatifRequests& rq, const char* fn) {
   if (!job) return ORH_E_INVALID;
   orh_ctx* ctx = job->g->ctx;
   join_deferred(ctx);
-  if (n_req == 0) return ORH_OK;
-  if (!h_src_idx || !h_ignore_ptr || (h_ignore_ptr[n_req] && !h_ignore_links) || !d_dist || !d_nh)
-    return fail(ctx, ORH_E_INVALID, "orh_whatif_run: null argument");
+  const uint32_t n = rq.n_req;
+  if (n == 0) return ORH_OK;
+  if (!rq.src_idx || !rq.ign_ptr || (rq.ign_ptr[n] && !rq.ign_links) ||
+      (rq.drn_ptr && rq.drn_ptr[n] && !rq.drn_nodes) || (rq.met_ptr && rq.met_ptr[n] && !rq.mets) || !rq.d_dist ||
+      !rq.d_nh)
+    return fail(ctx, ORH_E_INVALID, std::string(fn) + ": null argument");
   if (job->gen != job->g->gen)
-    return fail(ctx, ORH_E_STATE, "orh_whatif_run: the graph changed since the job was created");
+    return fail(ctx, ORH_E_STATE, std::string(fn) + ": the graph changed since the job was created");
   hipSetDevice(ctx->device);
-  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, nullptr, nullptr, nullptr, nullptr, d_dist,
-                    d_nh, d_info);
+  return whatif_run(job, rq);
+}
+
+int orh_whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
+                   const uint32_t* h_ignore_links, uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info) {
+  return checked_run(job, WhatifRequests{n_req, h_src_idx, h_ignore_ptr, h_ignore_links, nullptr, nullptr, nullptr,
+                                         nullptr, d_dist, d_nh, d_info},
+                     "orh_whatif_run");
 }
 
 int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
                           const uint32_t* h_ignore_links, const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
                           uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info) {
-  if (!job) return ORH_E_INVALID;
-  orh_ctx* ctx = job->g->ctx;
-  join_deferred(ctx);
-  if (n_req == 0) return ORH_OK;
-  if (!h_src_idx || !h_ignore_ptr || (h_ignore_ptr[n_req] && !h_ignore_links) ||
-      (h_drain_ptr && h_drain_ptr[n_req] && !h_drain_nodes) || !d_dist || !d_nh)
-    return fail(ctx, ORH_E_INVALID, "orh_whatif_run_drains: null argument");
-  if (job->gen != job->g->gen)
-    return fail(ctx, ORH_E_STATE, "orh_whatif_run_drains: the graph changed since the job was created");
-  hipSetDevice(ctx->device);
-  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes, nullptr,
-                    nullptr, d_dist, d_nh, d_info);
+  return checked_run(job, WhatifRequests{n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes,
+                                         nullptr, nullptr, d_dist, d_nh, d_info},
+                     "orh_whatif_run_drains");
 }
 
 int orh_whatif_run_metrics(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
                            const uint32_t* h_ignore_links, const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
                            const uint32_t* h_metric_ptr, const orh_whatif_metric* h_metrics, uint32_t* d_dist,
                            uint32_t* d_nh, uint32_t* d_info) {
-  if (!job) return ORH_E_INVALID;
-  orh_ctx* ctx = job->g->ctx;
-  join_deferred(ctx);
-  if (n_req == 0) return ORH_OK;
-  if (!h_src_idx || !h_ignore_ptr || (h_ignore_ptr[n_req] && !h_ignore_links) ||
-      (h_drain_ptr && h_drain_ptr[n_req] && !h_drain_nodes) ||
-      (h_metric_ptr && h_metric_ptr[n_req] && !h_metrics) || !d_dist || !d_nh)
-    return fail(ctx, ORH_E_INVALID, "orh_whatif_run_metrics: null argument");
-  if (job->gen != job->g->gen)
-    return fail(ctx, ORH_E_STATE, "orh_whatif_run_metrics: the graph changed since the job was created");
-  hipSetDevice(ctx->device);
-  return whatif_run(job, n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes, h_metric_ptr,
-                    h_metrics, d_dist, d_nh, d_info);
+  return checked_run(job, WhatifRequests{n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes,
+                                         h_metric_ptr, h_metrics, d_dist, d_nh, d_info},
+                     "orh_whatif_run_metrics");
 }
+
 
 int orh_whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* d_dist,
                       const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_impact_opts* opts,
@@ -2366,24 +2439,23 @@ int orh_whatif_destroy(orh_whatif* job) {
   hipStreamSynchronize(job->g->ctx->stream);
   for (hipStream_t t : job->t3)
     if (t) hipStreamDestroy(t);
+  auto release = [](StageBuf& b) {
+    if (b.ev) {
+      hipEventSynchronize(b.ev);
+      hipEventDestroy(b.ev);
+    }
+    if (b.h) hipHostFree(b.h);
+    hipFree(b.d);
+  };
   for (int c = 0; c < kRunSlots; ++c) {
-    hipFree(job->t3_slots[c]);
-    if (job->mid_ev[c]) hipEventDestroy(job->mid_ev[c]);
-    hipFree(job->d_work[c]);
-    if (job->front_ev[c]) hipEventDestroy(job->front_ev[c]);
-    if (job->side_ev[c]) hipEventDestroy(job->side_ev[c]);
-    if (job->stage_ev[c]) {
-      hipEventSynchronize(job->stage_ev[c]);
-      hipEventDestroy(job->stage_ev[c]);
-    }
-    if (job->h_stage[c]) hipHostFree(job->h_stage[c]);
-    hipFree(job->d_stage[c]);
-    if (job->imp_ev[c]) {
-      hipEventSynchronize(job->imp_ev[c]);
-      hipEventDestroy(job->imp_ev[c]);
-    }
-    if (job->h_imp[c]) hipHostFree(job->h_imp[c]);
-    hipFree(job->d_imp[c]);
+    RunSlot& r = job->run[c];
+    hipFree(r.t3_slots);
+    if (r.mid_ev) hipEventDestroy(r.mid_ev);
+    hipFree(r.d_work);
+    if (r.front_ev) hipEventDestroy(r.front_ev);
+    if (r.side_ev) hipEventDestroy(r.side_ev);
+    release(r.stage);
+    release(job->imp[c]);
   }
   hipFree(job->d_base);
   hipFree(job->own_slots);
