@@ -322,7 +322,7 @@ int orh_spf_batch_exact(orh_graph* g, const orh_spf_request* req, uint32_t words
 #define ORH_GRAPH_WIDE_METRIC 2u /* link-metric path sums can reach 2^32 - 1 */
 int orh_graph_flags(const orh_graph* g, uint32_t* flags);
 
-/* ---- what-if jobs (batched link-failure, node-drain and cost-out SPFs) ---
+/* ---- what-if jobs (batched link-failure, node-drain, cost-out and cost-in SPFs) ---
  * runSpf(src, useLinkMetric, linksToIgnore) (LinkState.cpp:808-882) for many
  * (source, ignore set) requests over a fixed source set - the C4 shape,
  * "4,096 links x 64 sources" (SURVEY.md §8d). orh_whatif_create searches the
@@ -338,6 +338,9 @@ int orh_graph_flags(const orh_graph* g, uint32_t* flags);
  * orh_whatif_run_metrics adds, per request, a set of metric raises (a link
  * costed out from one end or both, Link::setMetricFromNode, :640-710): the
  * rows change only below a raised record that was tight, and are as exact.
+ * orh_whatif_run_lowers adds, per request, a set of metric lowers (a link
+ * costed back in): a second pass behind the repair lets distances fall and
+ * first-hop masks widen below the lowered records, as exactly.
  * A job is bound to the graph structure it was created on
  * (ORH_E_STATE after a delta or reload). Everything is asynchronous on the
  * context stream; one mask word per node (every source has <= 32 distinct
@@ -376,8 +379,8 @@ int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src
  *   raised to infinity), so the same repair covers it: the rows change only
  *   below a raised record that is tight under its old metric, and the
  *   re-derivation weighs a raised record with its new metric. A lower metric
- *   shortens paths, which the repair cannot do: that stays a topology change
- *   (orh_graph_patch_edges + orh_whatif_refresh) and is rejected here.
+ *   shortens paths, which the repair cannot do: it goes into the h_lowers of
+ *   orh_whatif_run_lowers and is rejected here.
  * - A link both ignored and raised in one request is ignored. Of several
  *   raises of one (link, end) in a request the largest holds.
  * - A hop-count job (use_link_metric == 0) ignores metrics: its raises are
@@ -407,16 +410,71 @@ int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src
 typedef struct orh_whatif_metric {
   uint32_t link;      /* orh_csr link id */
   uint32_t from_node; /* the end whose Link::getMetricFromNode changes; ORH_NO_NODE: both ends */
-  uint32_t metric;    /* new value, >= the current one */
+  uint32_t metric;    /* new value: >= the current one in h_metrics, <= it in h_lowers */
 } orh_whatif_metric;
 int orh_whatif_run_metrics(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx,
                            const uint32_t* h_ignore_ptr, const uint32_t* h_ignore_links,
                            const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
                            const uint32_t* h_metric_ptr, const orh_whatif_metric* h_metrics,
                            uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info);
+/* orh_whatif_run_metrics with, per request, a set of metric lowers: costing a
+ * link back in, or lowering its metric. Lower k of request i, h_lowers[
+ * h_lower_ptr[i] .. h_lower_ptr[i+1]), replaces what
+ * Link::getMetricFromNode(from_node) returns for that link (metric = the new
+ * value, from_node = the end, or ORH_NO_NODE for both), and the request's row
+ * is runSpf(src_i, use_link_metric, ignore_i) on the graph with the raised and
+ * the lowered metrics replaced and the drained nodes overloaded, bit-identical
+ * in distances and first-hop masks. h_lower_ptr == NULL: exactly
+ * orh_whatif_run_metrics (which keeps rejecting a decrease in h_metrics).
+ * - Two stages per request. The first is the run without the lowers. The
+ *   second, for the requests with an effective lower, lets distances fall
+ *   from the lowered records (a label-correcting wave), then re-derives the
+ *   first-hop masks of every node whose distance fell or that gained an
+ *   equal-cost path, closed under the records tight in the new distances.
+ *   It is queued behind the run's last tier, so orh_whatif_flush, a later run
+ *   into the same buffers and orh_whatif_impact wait for it as for any run.
+ * - A link both ignored and lowered in one request is ignored. Of several
+ *   lowers of one (link, end) in a request the smallest holds. A lowered
+ *   record out of a node that is overloaded, or drained in this request,
+ *   carries no transit as before.
+ * - A hop-count job (use_link_metric == 0) ignores metrics: its lowers are
+ *   validated and then do nothing.
+ * - Validation, all before anything is queued, per lower in this order: a
+ *   link id >= n_links or a free link slot is skipped, as in ignore sets;
+ *   from_node that is neither ORH_NO_NODE nor an end of the link:
+ *   ORH_E_INVALID; a link that is down: no-op (restoring a down link stays a
+ *   topology change: orh_graph_patch_edges + orh_whatif_refresh); metric == 0:
+ *   ORH_E_UNSUPPORTED (jobs have no zero-metric links); metric above the
+ *   current w_out of a direction it names: ORH_E_INVALID; equal to it: that
+ *   direction is dropped; a (link, end) that the request's h_metrics name as
+ *   well: ORH_E_INVALID. NULL job: ORH_E_INVALID without touching a device.
+ * - Like a raise, an effective lower keeps its run off the full search (the
+ *   search's bucket widths are planned from the graph's metric range, which a
+ *   lower leaves): ORH_WHATIF_SEARCH_LARGE and ORH_WHATIF_FULL are ignored for
+ *   that run, and on a graph without tier-3 slots it is ORH_E_UNSUPPORTED. No
+ *   request fails for size on a graph that has slots: the second stage keeps
+ *   its node list and labels in LDS, and a request that outgrows them
+ *   finishes with its state in a global slot sized for the whole graph.
+ * - d_info: where the second stage re-derived at least one node the word is
+ *   ORH_WHATIF_TIER_LOWERED with ORH_WHATIF_AFFECTED = the first stage's count
+ *   plus the second's; otherwise the first stage's word stands (a lower to
+ *   the current value, or one that changes nothing, leaves 0).
+ * - ORH_WHATIF_SHARE_BASE: a request with an effective lower owns its row; it
+ *   is written even where the word stays tier 0, which still means "equal to
+ *   the base row".
+ * - orh_whatif_impact's classes assume that no node is nearer than in the
+ *   base row: rows of a request with an effective lower are outside its
+ *   contract (a "gain" summary does not exist yet). */
+int orh_whatif_run_lowers(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx,
+                          const uint32_t* h_ignore_ptr, const uint32_t* h_ignore_links,
+                          const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
+                          const uint32_t* h_metric_ptr, const orh_whatif_metric* h_metrics,
+                          const uint32_t* h_lower_ptr, const orh_whatif_metric* h_lowers,
+                          uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info);
 #define ORH_WHATIF_TIER(x) ((x) & 7u) /* 0 source row, 1/2 LDS repair, 3 global-slot repair, 4 full search
                                          (subtrees too large for LDS, up to ORH_WHATIF_FULL per run; every
-                                         such request without slots) */
+                                         such request without slots), 5 re-derived by the lower pass */
+#define ORH_WHATIF_TIER_LOWERED 5u
 #define ORH_WHATIF_AFFECTED(x) ((x) >> 3)
 /* job flags (orh_whatif_set_flags, before a run):
  * ORH_WHATIF_SHARE_BASE  a request whose source row stands (tier 0) is not
@@ -449,7 +507,8 @@ int orh_whatif_flush(orh_whatif* job);
  * routes, reduced on the device while the request's row is still in its
  * buffer (a job's rows are far too many to copy out: C4 is 105 GB).
  * Request i's row (d_dist + i*N, d_nh + i*N, one mask word per node: the rows
- * an orh_whatif_run / _run_drains / _run_metrics of this job wrote) is compared with the
+ * an orh_whatif_run / _run_drains / _run_metrics of this job wrote; rows of a
+ * request with an effective lower are outside the contract) is compared with the
  * job's base row of source h_src_idx[i] (orh_whatif_base_rows), node by node.
  * A node unreached in the base row is in no class, and neither is the
  * request's source. */

@@ -688,7 +688,7 @@ py::tuple nodeImpactArrays(const Job& b, size_t n) {
   return py::make_tuple(lost, moved);
 }
 
-// what_if_batch(metric=...): per request a list of (link_id, from_name or
+// what_if_batch(metric=... / lower=...): per request a list of (link_id, from_name or
 // None for both ends, new_metric)
 using PyMetricRaises = std::vector<std::vector<std::tuple<uint32_t, std::optional<std::string>, uint32_t>>>;
 
@@ -961,16 +961,18 @@ PYBIND11_MODULE(_openr_host, m) {
            [](const LinkState& s, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric,
               bool shareBase, bool searchLarge, const std::optional<std::vector<std::vector<std::string>>>& drain,
-              const std::optional<PyMetricRaises>& metric) {
+              const std::optional<PyMetricRaises>& metric, const std::optional<PyMetricRaises>& lower) {
              // drain: per request the node names it treats as overloaded (None: no drains)
              // metric: per request its (link_id, from_name_or_None, new_metric) raises (None: none)
+             // lower: per request its metric lowers, the same triples (None: none)
              return new WhatIfBatch(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase, searchLarge,
                                     drain ? *drain : std::vector<std::vector<std::string>>{},
-                                    metric ? metricRaises(*metric) : std::vector<std::vector<WhatIfMetricRaise>>{});
+                                    metric ? metricRaises(*metric) : std::vector<std::vector<WhatIfMetricRaise>>{},
+                                    lower ? metricRaises(*lower) : std::vector<std::vector<WhatIfMetricLower>>{});
            },
            py::arg("srcs"), py::arg("src_idx"), py::arg("ignore"), py::arg("chunk") = 4096,
            py::arg("use_link_metric") = true, py::arg("share_base") = false, py::arg("search_large") = false,
-           py::arg("drain") = py::none(), py::arg("metric") = py::none(),
+           py::arg("drain") = py::none(), py::arg("metric") = py::none(), py::arg("lower") = py::none(),
            py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
       .def("run_spf_batch",
            [](const LinkState& s, const std::vector<std::string>& srcs,
@@ -1067,14 +1069,16 @@ PYBIND11_MODULE(_openr_host, m) {
            [](const ReplicatedLinkState& s, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric,
               bool shareBase, const std::optional<std::vector<std::vector<std::string>>>& drain,
-              const std::optional<PyMetricRaises>& metric) {
+              const std::optional<PyMetricRaises>& metric, const std::optional<PyMetricRaises>& lower) {
              return new MultiDeviceWhatIf(s, srcs, srcIdx, ignore, chunk, useLinkMetric, shareBase,
                                           drain ? *drain : std::vector<std::vector<std::string>>{},
-                                          metric ? metricRaises(*metric) : std::vector<std::vector<WhatIfMetricRaise>>{});
+                                          metric ? metricRaises(*metric) : std::vector<std::vector<WhatIfMetricRaise>>{},
+                                          lower ? metricRaises(*lower) : std::vector<std::vector<WhatIfMetricLower>>{});
            },
            py::arg("srcs"), py::arg("src_idx"), py::arg("ignore"), py::arg("chunk") = 4096,
            py::arg("use_link_metric") = true, py::arg("share_base") = false, py::arg("drain") = py::none(),
-           py::arg("metric") = py::none(), py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
+           py::arg("metric") = py::none(), py::arg("lower") = py::none(),
+           py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
       .def("kth_paths_batch",
            [](const ReplicatedLinkState& s, const std::vector<std::pair<std::string, std::string>>& pairs) {
              return new MultiDeviceKthPaths(s, pairs);

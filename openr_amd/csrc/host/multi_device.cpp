@@ -243,13 +243,16 @@ MultiDeviceWhatIf::MultiDeviceWhatIf(const ReplicatedLinkState& rls, const std::
                                      const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk,
                                      bool useLinkMetric, bool shareBase,
                                      const std::vector<std::vector<std::string>>& drain,
-                                     const std::vector<std::vector<WhatIfMetricRaise>>& metric)
+                                     const std::vector<std::vector<WhatIfMetricRaise>>& metric,
+                                     const std::vector<std::vector<WhatIfMetricLower>>& lower)
     : total_(srcIdx.size()) {
   if (srcIdx.size() != ignore.size()) throw std::invalid_argument("MultiDeviceWhatIf: one ignore set per request");
   if (!drain.empty() && drain.size() != srcIdx.size())
     throw std::invalid_argument("MultiDeviceWhatIf: one drain set per request (or none at all)");
   if (!metric.empty() && metric.size() != srcIdx.size())
     throw std::invalid_argument("MultiDeviceWhatIf: one list of metric raises per request (or none at all)");
+  if (!lower.empty() && lower.size() != srcIdx.size())
+    throw std::invalid_argument("MultiDeviceWhatIf: one list of metric lowers per request (or none at all)");
   const size_t world = rls.replicas();
   // link ids name the same link on every replica (the same updates applied
   // in the same order); check the cheap invariant
@@ -280,6 +283,7 @@ MultiDeviceWhatIf::MultiDeviceWhatIf(const ReplicatedLinkState& rls, const std::
     std::vector<std::vector<uint32_t>> bg;
     std::vector<std::vector<std::string>> bd;
     std::vector<std::vector<WhatIfMetricRaise>> bm;
+    std::vector<std::vector<WhatIfMetricLower>> bl;
     bi.reserve(b.reqs.size());
     bg.reserve(b.reqs.size());
     for (size_t i : b.reqs) {
@@ -287,6 +291,7 @@ MultiDeviceWhatIf::MultiDeviceWhatIf(const ReplicatedLinkState& rls, const std::
       bg.push_back(ignore[i]);
       if (!drain.empty()) bd.push_back(drain[i]);  // each block its own requests' drains
       if (!metric.empty()) bm.push_back(metric[i]);  // and raises
+      if (!lower.empty()) bl.push_back(lower[i]);    // and lowers
     }
     // blocks of a 4-way or wider split are short jobs: their largest repairs
     // are searched in full (ORH_WHATIF_SEARCH_LARGE; rehearsal at 8 blocks:
@@ -300,7 +305,7 @@ MultiDeviceWhatIf::MultiDeviceWhatIf(const ReplicatedLinkState& rls, const std::
     const uint32_t n = static_cast<uint32_t>(b.reqs.size());
     const uint32_t bchunk = std::max<uint32_t>(1, std::min(chunk, (n + minChunks - 1) / minChunks));
     b.job = std::make_unique<WhatIfBatch>(rls.replica(r), bs, bi, bg, bchunk, useLinkMetric, shareBase,
-                                          world >= kSearchLargeBlocks, bd, bm);
+                                          world >= kSearchLargeBlocks, bd, bm, bl);
   }
 }
 

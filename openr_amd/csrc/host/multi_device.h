@@ -99,7 +99,8 @@ class MultiDeviceSweep {
 // of the prefix sums at k/world of the total (block r = [cuts[r], cuts[r+1]))
 std::vector<size_t> equalWorkCuts(const std::vector<double>& w, size_t world);
 
-// A what-if job (WhatIfBatch: requests (source, ignored links, drained nodes, metric raises)) split over a
+// A what-if job (WhatIfBatch: requests (source, ignored links, drained nodes, metric raises and
+// lowers)) split over a
 // ReplicatedLinkState's devices by source: the sources are cut into
 // contiguous blocks of equal request counts, and device r's job holds the
 // base rows of block r's sources and runs exactly their requests (SURVEY.md
@@ -114,7 +115,8 @@ class MultiDeviceWhatIf {
                     const std::vector<uint32_t>& srcIdx, const std::vector<std::vector<uint32_t>>& ignore,
                     uint32_t chunk, bool useLinkMetric = true, bool shareBase = false,
                     const std::vector<std::vector<std::string>>& drain = {},
-                    const std::vector<std::vector<WhatIfMetricRaise>>& metric = {});
+                    const std::vector<std::vector<WhatIfMetricRaise>>& metric = {},
+                    const std::vector<std::vector<WhatIfMetricLower>>& lower = {});
   MultiDeviceWhatIf(const MultiDeviceWhatIf&) = delete;
   MultiDeviceWhatIf& operator=(const MultiDeviceWhatIf&) = delete;
   // every block at once: one host thread per device drives its job

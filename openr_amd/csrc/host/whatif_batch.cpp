@@ -20,7 +20,8 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
                          const std::vector<uint32_t>& srcIdx, const std::vector<std::vector<uint32_t>>& ignore,
                          uint32_t chunk, bool useLinkMetric, bool shareBase, bool searchLarge,
                          const std::vector<std::vector<std::string>>& drain,
-                         const std::vector<std::vector<WhatIfMetricRaise>>& metric)
+                         const std::vector<std::vector<WhatIfMetricRaise>>& metric,
+                         const std::vector<std::vector<WhatIfMetricLower>>& lower)
     : ls_(ls), useLinkMetric_(useLinkMetric), shareBase_(shareBase), searchLarge_(searchLarge) {
   if (srcIdx.size() != ignore.size()) throw std::invalid_argument("WhatIfBatch: one ignore set per request");
   if (!drain.empty() && drain.size() != srcIdx.size())
@@ -35,18 +36,26 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
     }
   if (!metric.empty() && metric.size() != srcIdx.size())
     throw std::invalid_argument("WhatIfBatch: one list of metric raises per request (or none at all)");
-  std::vector<std::vector<orh_whatif_metric>> raiseIds(metric.size());
-  for (size_t i = 0; i < metric.size(); ++i)
-    for (const auto& mr : metric[i]) {
-      uint32_t from = ORH_NO_NODE;
-      if (!mr.from.empty()) {
-        auto id = ls.nodeId(mr.from);
-        if (!id) throw std::invalid_argument("WhatIfBatch: unknown node " + mr.from + " in a metric raise");
-        from = *id;
+  if (!lower.empty() && lower.size() != srcIdx.size())
+    throw std::invalid_argument("WhatIfBatch: one list of metric lowers per request (or none at all)");
+  // a list of metric changes by node id; *any: some request has one
+  auto resolve = [&](const std::vector<std::vector<WhatIfMetricRaise>>& in, const char* what, bool* any) {
+    std::vector<std::vector<orh_whatif_metric>> ids(in.size());
+    for (size_t i = 0; i < in.size(); ++i)
+      for (const auto& mr : in[i]) {
+        uint32_t from = ORH_NO_NODE;
+        if (!mr.from.empty()) {
+          auto id = ls.nodeId(mr.from);
+          if (!id) throw std::invalid_argument("WhatIfBatch: unknown node " + mr.from + " in a metric " + what);
+          from = *id;
+        }
+        ids[i].push_back({mr.link, from, mr.metric});
+        *any = true;
       }
-      raiseIds[i].push_back({mr.link, from, mr.metric});
-      raises_ = true;
-    }
+    return ids;
+  };
+  const auto raiseIds = resolve(metric, "raise", &raises_);
+  const auto lowerIds = resolve(lower, "lower", &lowers_);
   if (chunk == 0) throw std::invalid_argument("WhatIfBatch: chunk must be positive");
   for (const auto& s : srcs) {
     auto id = ls.nodeId(s);
@@ -61,8 +70,8 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
   chunk_ = static_cast<uint32_t>(std::min<size_t>(chunk, std::max<size_t>(n, 1)));
   for (size_t c0 = 0; c0 < n; c0 += chunk_) {
     const size_t c1 = std::min(n, c0 + chunk_);
-    std::vector<uint32_t> ptr{0}, links, dptr, dnodes, mptr;
-    std::vector<orh_whatif_metric> mets;
+    std::vector<uint32_t> ptr{0}, links, dptr, dnodes, mptr, lptr;
+    std::vector<orh_whatif_metric> mets, lows;
     for (size_t i = c0; i < c1; ++i) {
       links.insert(links.end(), ignore[i].begin(), ignore[i].end());
       ptr.push_back(static_cast<uint32_t>(links.size()));
@@ -84,8 +93,16 @@ WhatIfBatch::WhatIfBatch(const LinkState& ls, const std::vector<std::string>& sr
       }
       if (mets.empty()) mets.push_back({0u, ORH_NO_NODE, 0u});
     }
+    if (lowers_) {
+      lptr.push_back(0);
+      for (size_t i = c0; i < c1; ++i) {
+        lows.insert(lows.end(), lowerIds[i].begin(), lowerIds[i].end());
+        lptr.push_back(static_cast<uint32_t>(lows.size()));
+      }
+      if (lows.empty()) lows.push_back({0u, ORH_NO_NODE, 0u});
+    }
     chunks_.push_back({c0, c1, std::move(ptr), std::move(links), std::move(dptr), std::move(dnodes),
-                       std::move(mptr), std::move(mets)});
+                       std::move(mptr), std::move(mets), std::move(lptr), std::move(lows)});
   }
   graph_ = ls.deviceGraph();
   ctx_ = ls.context();
@@ -217,6 +234,8 @@ void WhatIfBatch::nodeImpact(uint32_t* lost, uint32_t* moved) const {
 
 void WhatIfBatch::run() {
   impactRan_ = false;
+  if (impact_ && lowers_)  // the summary's classes assume that no node gets nearer
+    throw std::invalid_argument("WhatIfBatch: impact summaries do not cover requests that lower metrics");
   if (impact_) {  // buffers of the mode; the node counters start at zero (before the job's clock)
     auto alloc = [&](auto** p, size_t bytes) {
       if (!*p) check(ctx_, orh_device_alloc(ctx_, std::max<size_t>(bytes, 8), reinterpret_cast<void**>(p)),
@@ -273,7 +292,14 @@ void WhatIfBatch::run() {
     // this run overwrites the rows of chunk c - nBuf_, and waits for them by
     // itself: their summary goes right before it
     if (impact_ && c >= static_cast<size_t>(nBuf_)) queueImpact(c - nBuf_);
-    if (raises_)
+    if (lowers_)
+      check(ctx_,
+            orh_whatif_run_lowers(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(),
+                                  drains_ ? ch.drnPtr.data() : nullptr, drains_ ? ch.drnNodes.data() : nullptr,
+                                  raises_ ? ch.metPtr.data() : nullptr, raises_ ? ch.mets.data() : nullptr,
+                                  ch.lowPtr.data(), ch.lows.data(), dDist_[b], dNh_[b], dInfo_ + ch.lo),
+            "orh_whatif_run_lowers");
+    else if (raises_)
       check(ctx_,
             orh_whatif_run_metrics(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(),
                                    drains_ ? ch.drnPtr.data() : nullptr, drains_ ? ch.drnNodes.data() : nullptr,

@@ -7,7 +7,9 @@
 // tight out-link of a drained node, where the job re-derives it (bit-identical
 // to a fresh runSpf). A request may also raise link metrics (cost a link out,
 // Link::setMetricFromNode, :640-710): the same repair below the raised records
-// that were tight, with the raised weights.
+// that were tight, with the raised weights. And it may lower them (cost a
+// link back in): a second pass behind the repair lets distances fall and
+// first-hop masks widen below the lowered records.
 //
 // This is the library form a caller outside Python drives (the bench, the
 // multi-device split in multi_device.h); the Python binding wraps it.
@@ -30,6 +32,10 @@ struct WhatIfMetricRaise {
   uint32_t metric;
 };
 
+// One metric lower (costing a link back in): the same triple, `metric` <= the
+// current one.
+using WhatIfMetricLower = WhatIfMetricRaise;
+
 class WhatIfBatch {
  public:
   // request i = (srcs[srcIdx[i]], ignore[i]) with ignore sets of LinkState link
@@ -42,12 +48,16 @@ class WhatIfBatch {
   // std::invalid_argument. metric: per request its metric raises, with the
   // same conventions (empty: none at all; an unknown end name is
   // std::invalid_argument; a decrease fails the run, see
-  // orh_whatif_run_metrics)
+  // orh_whatif_run_metrics). lower: per request its metric lowers, same
+  // conventions (an increase fails the run, see orh_whatif_run_lowers); a
+  // batch with lowers takes no impact summaries (run() throws
+  // std::invalid_argument with setImpact(true))
   WhatIfBatch(const LinkState& ls, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric = true,
               bool shareBase = false, bool searchLarge = false,
               const std::vector<std::vector<std::string>>& drain = {},
-              const std::vector<std::vector<WhatIfMetricRaise>>& metric = {});
+              const std::vector<std::vector<WhatIfMetricRaise>>& metric = {},
+              const std::vector<std::vector<WhatIfMetricLower>>& lower = {});
   ~WhatIfBatch();
   WhatIfBatch(const WhatIfBatch&) = delete;
   WhatIfBatch& operator=(const WhatIfBatch&) = delete;
@@ -101,6 +111,8 @@ class WhatIfBatch {
     std::vector<uint32_t> drnPtr, drnNodes;  // drained node ids, rebased like the ignore CSR
     std::vector<uint32_t> metPtr;            // metric raises, rebased the same way
     std::vector<orh_whatif_metric> mets;
+    std::vector<uint32_t> lowPtr;            // metric lowers, likewise
+    std::vector<orh_whatif_metric> lows;
   };
   void allocate();
   const LinkState& ls_;
@@ -110,6 +122,7 @@ class WhatIfBatch {
   bool digests_{false};
   bool drains_{false};  // some request drains a node: runs go through orh_whatif_run_drains
   bool raises_{false};  // some request raises a metric: runs go through orh_whatif_run_metrics
+  bool lowers_{false};  // some request lowers a metric: runs go through orh_whatif_run_lowers
   std::vector<uint32_t> srcs_, srcIdx_;
   std::vector<Chunk> chunks_;
   uint32_t chunk_{1};

@@ -1,5 +1,6 @@
-// Internal interface of the what-if repair kernels (whatif_kernels.hip) and
-// the impact summaries over their rows (whatif_impact_kernels.hip).
+// Internal interface of the what-if repair kernels (whatif_kernels.hip), the
+// metric-lower pass behind them (whatif_lower_kernels.hip) and the impact
+// summaries over their rows (whatif_impact_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,9 +30,11 @@ namespace orh {
 // rse carry (record, new weight); a run with raises takes no full search.
 constexpr uint32_t kWhatifTierBase = 0, kWhatifTierSmall = 1, kWhatifTierLarge = 2, kWhatifTierSlot = 3,
                    kWhatifTierSearch = 4;
+// a row that the lower pass re-derived behind the tiers (whatif_lower_kernels.hip)
+constexpr uint32_t kWhatifTierLowered = 5;
 constexpr uint32_t kSmallA = 256, kSmallE = 1024;
 // counters (u32, zeroed before a run): per queue q = 0..2 its length and the
-// next index to claim
+// next index to claim; the last two are the lower pass's slot queue
 constexpr uint32_t kWhatifCounters = 8;
 
 struct RepairArgs {
@@ -107,6 +110,26 @@ hipError_t launch_repair_back(const RepairArgs& a, uint32_t ell_k, size_t lds_li
 // not wait for this run's largest repairs
 hipError_t launch_repair_back_split(const RepairArgs& a, uint32_t ell_k, size_t lds_limit, hipStream_t s,
                                     hipStream_t s3, hipEvent_t mid);
+
+// ---- metric lowers (whatif_lower_kernels.hip) -----------------------------
+// Stage 2 of the requests of a run that lower link metrics: each one's row,
+// as the repair tiers left it, becomes the exact row of the graph with the
+// lowered records as well (the kernel file has the rule and why it is exact).
+struct LowerArgs {
+  uint32_t n_low;           // requests with at least one effective lower
+  const uint32_t* req;      // [n_low] their request ids, ascending
+  const uint32_t* rec_ptr;  // [n_low + 1]
+  const uint4* recs;        // lowered records: (tail, head, record tail -> head, lowered weight)
+  const uint32_t* wl_ptr;   // [n_low + 1]
+  const uint2* wl;          // per request (record, weight) sorted by record: its lowers and its raises
+  uint32_t* queue;          // [n_low] list positions whose sets outgrew the LDS caps (slot pass)
+  uint32_t cap_a, cap_e;    // LDS caps of the first pass: nodes of M, predecessor edges among them
+};
+// LDS bytes of the first pass for the given caps
+size_t lower_lds_bytes(uint32_t n_nodes, uint32_t cap_a, uint32_t cap_e);
+// both passes on stream s, behind the run's last tier: the LDS pass, then the
+// slot pass over a.slot_mem (a.n_slots > 0) for what outgrew it
+hipError_t launch_lower(const RepairArgs& a, const LowerArgs& l, uint32_t ell_k, size_t lds_limit, hipStream_t s);
 
 // per row r < rows: the digest of (dist[r][v], nh[r][v][0..words)) over v < n
 // (row_digest_kernel), into out[r]

@@ -86,65 +86,13 @@
 #include <algorithm>
 
 #include "spf_device.h"  // edge record flags, ignored()
+#include "whatif_device.h"  // meet, bar, for_records, cut_tight, relabel
 #include "whatif_kernels.h"
 
 namespace orh {
 namespace {
 
 constexpr uint32_t kSlotBlock = 1024;  // slot pass: few large affected sets, one per CU
-constexpr uint32_t kInfD = 0xFFFFFFFFu;
-constexpr unsigned long long kInfLab = 0xFFFFFFFF00000000ull;  // {dist = inf, mask = 0}
-
-// lattice meet of a label and the candidate {d, nh}: a smaller distance
-// replaces, an equal one ORs the mask
-__device__ inline unsigned long long meet(unsigned long long l, uint64_t d, uint32_t nh) {
-  if (d >= kInfD) return l;
-  const uint32_t ld = static_cast<uint32_t>(l >> 32);
-  if (d < ld) return (d << 32) | nh;
-  if (d == ld) return l | nh;
-  return l;
-}
-
-// workgroup barrier that first drains this wave's global stores: the repair
-// state (and the mask row used as index map) lives in global memory in the
-// slot pass, and other waves read it with plain loads after the barrier
-__device__ inline void bar() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-// the request's raised weight of record `rec`, else w: (record, new weight)
-// pairs sorted by record, a few entries; callers test n != 0 first
-__device__ inline uint32_t raised(const uint2* rse, uint32_t n, uint32_t rec, uint32_t w) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const uint2 x = rse[mid];
-    if (x.x == rec) return x.y;
-    if (x.x < rec) lo = mid + 1; else hi = mid;
-  }
-  return w;
-}
-
-// visit the live records of node v: ELL slots then the overflow list
-template <int K, class F>
-__device__ inline void for_records(const uint2* recs, uint32_t v, F&& f) {
-  const uint2* slots = recs + static_cast<size_t>(v) * K;
-  uint2 r[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) r[j] = slots[j];
-#pragma unroll
-  for (int j = 0; j < K; ++j)
-    if (!(r[j].x & (ORH_REC_SKIP | ORH_REC_CONT))) f(r[j], static_cast<uint32_t>(v * K + j));
-  if (r[K - 1].x & ORH_REC_CONT) {
-    const uint32_t start = r[K - 1].x & ORH_REC_COL_MASK;
-    for (uint32_t q = 0; q < r[K - 1].y; ++q) {
-      const uint2 o = recs[start + q];
-      if (!(o.x & ORH_REC_SKIP)) f(o, start + q);
-    }
-  }
-}
-
 constexpr uint32_t kCopyTile = 256 * 16;  // u32 elements of a row per copy workgroup
 
 // base rows -> request rows; vec: every row is 16-byte aligned (N % 4 == 0
@@ -188,23 +136,14 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
                                uint32_t* s_cnt, uint32_t* s_ecnt, uint32_t* s_ovf, uint32_t* s_flag) {
   const uint32_t N = a.n_nodes;
   const uint32_t tid = threadIdx.x, B = blockDim.x;
-  // state: labels u64[cap_a] | boundary labels u64[cap_a] | edges uint2[cap_e] |
-  //        edge ranges uint2[cap_a] | node list u32[cap_a] | membership bitmap u32[NB]
-  unsigned long long* lab = reinterpret_cast<unsigned long long*>(base);
-  unsigned long long* blab = lab + cap_a;
-  uint2* edges = reinterpret_cast<uint2*>(blab + cap_a);
-  uint2* erange = edges + cap_e;
-  uint32_t* alist = reinterpret_cast<uint32_t*>(erange + cap_a);
-  uint32_t* bits = alist + cap_a;
+  const RepairState st(base, cap_a, cap_e);  // the layout: whatif_device.h
+  uint32_t* alist = st.alist;
+  uint32_t* bits = st.bits;
 
   const uint32_t s = a.srcs[r];
   const size_t b = a.base_row[r];
   const uint32_t* bd = a.base_dist + b * N;
   const uint32_t* bn = a.base_nh + b * N;
-  uint32_t* od = a.out_dist + static_cast<size_t>(r) * N;
-  uint32_t* on = a.out_nh + static_cast<size_t>(r) * N;
-  const uint32_t* ign = a.ign + a.ign_ptr[r];
-  const uint32_t n_ign = a.ign_ptr[r + 1] - a.ign_ptr[r];
   const bool metric = a.use_link_metric != 0;
   // the request's drained nodes (sorted; never s): no transit, like ovl
   const uint32_t* drn = nullptr;
@@ -242,11 +181,7 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
   // their own; tight means tight under the record's own, old weight)
   for (uint32_t c = a.cut_ptr[r] + tid; c < a.cut_ptr[r + 1]; c += B) {
     const uint4 cut = a.cuts[c];  // (tail, head, record of tail -> head, 0)
-    const uint2 rec = a.recs[cut.z];
-    if (rec.x & ORH_REC_SKIP) continue;  // link down: never on a path
-    const uint32_t dx = bd[cut.x];
-    if (dx == kInfD || (cut.x != s && a.ovl[cut.x])) continue;
-    if (static_cast<uint64_t>(dx) + (metric ? rec.y : 1u) == bd[cut.y]) add(cut.y);
+    if (cut_tight(a, bd, s, cut)) add(cut.y);
   }
   bar();
   if (*s_cnt == 0u) return 0u;  // nothing below a tight ignored link: the base row stands
@@ -275,97 +210,9 @@ __device__ uint32_t repair_one(const RepairArgs& a, uint32_t r, uint32_t* base, 
   }
   const uint32_t n = min(*s_cnt, cap_a);
   if (*s_ovf) return ~0u;
-  // the request's mask row doubles as the node -> A index map (rewritten below)
-  for (uint32_t k = tid; k < n; k += B) on[alist[k]] = k;
-  bar();
-
-  // boundary labels from predecessors outside A; edges from those inside
-  auto pred = [&](const uint2& rec, uint32_t q, auto&& inside, auto&& outside) {
-    if (n_ign && ignored(ign, n_ign, a.link[q])) return;
-    const uint32_t p = rec.x & ORH_REC_COL_MASK;
-    const uint32_t q2 = a.rev[q];
-    const uint2 back = a.recs[q2];  // p -> v: p's metric and p's overload bit
-    if (p != s && (back.x & ORH_REC_ROW_OVL)) return;
-    if constexpr (kDrain)
-      if (n_drn && p != s && drained(drn, n_drn, p)) return;
-    uint32_t w = metric ? back.y : 1u;
-    if constexpr (kRaise)
-      if (n_rse) w = raised(rse, n_rse, q2, w);  // staged for metric jobs only
-    if (bits[p >> 5] & (1u << (p & 31u))) inside(p, w);
-    else outside(p, q2, w);
-  };
-  for (uint32_t k = tid; k < n; k += B) {
-    const uint32_t v = alist[k];
-    uint32_t cnt = 0;
-    unsigned long long bl = kInfLab;
-    for_records<K>(a.recs, v, [&](const uint2& rec, uint32_t q) {
-      pred(rec, q, [&](uint32_t, uint32_t) { ++cnt; },
-           [&](uint32_t p, uint32_t q2, uint32_t w) {
-             const uint32_t dp = bd[p];
-             if (dp == kInfD) return;
-             bl = meet(bl, static_cast<uint64_t>(dp) + w, p == s ? (1u << a.rank_out[q2]) : bn[p]);
-           });
-    });
-    const uint32_t e0 = cnt ? atomicAdd(s_ecnt, cnt) : 0u;
-    if (e0 + cnt > cap_e) {
-      *s_ovf = 1u;
-      cnt = 0;
-    }
-    uint32_t e = e0;
-    if (cnt)
-      for_records<K>(a.recs, v, [&](const uint2& rec, uint32_t q) {
-        pred(rec, q, [&](uint32_t p, uint32_t w) { edges[e++] = make_uint2(on[p], w); },
-             [](uint32_t, uint32_t, uint32_t) {});
-      });
-    erange[k] = make_uint2(e0, e0 + cnt);
-    blab[k] = bl;
-    lab[k] = kInfLab;
-  }
-  bar();
-  if (*s_ovf) return ~0u;
-
-  // chaotic relaxation inside A until no label changes (labels only descend
-  // in the lattice; a sweep that writes nothing proves the fixpoint)
-  for (uint32_t it = 0;; ++it) {
-    bool changed = false;
-    for (uint32_t k = tid; k < n; k += B) {
-      unsigned long long nl = blab[k];
-      const uint2 er = erange[k];
-      uint32_t e = er.x;
-      for (; e + 4 <= er.y; e += 4) {  // four predecessor labels in flight
-        uint2 ed[4];
-        unsigned long long lj[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ed[q] = edges[e + q];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) lj[q] = lab[ed[q].x];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) nl = meet(nl, (lj[q] >> 32) + ed[q].y, static_cast<uint32_t>(lj[q]));
-      }
-      for (; e < er.y; ++e) {
-        const uint2 ed = edges[e];
-        const unsigned long long lj = lab[ed.x];
-        nl = meet(nl, (lj >> 32) + ed.y, static_cast<uint32_t>(lj));
-      }
-      if (nl != lab[k]) {
-        lab[k] = nl;
-        changed = true;
-      }
-    }
-    const uint32_t par = it % 3u;
-    if (changed) s_flag[par] = 1u;
-    bar();
-    const bool more = s_flag[par] != 0u;
-    if (tid == 0) s_flag[(par + 2u) % 3u] = 0u;  // the previous sweep's flag, read before this barrier
-    if (!more) break;
-  }
-  for (uint32_t k = tid; k < n; k += B) {
-    const uint32_t v = alist[k];
-    const unsigned long long l = lab[k];
-    od[v] = static_cast<uint32_t>(l >> 32);
-    on[v] = static_cast<uint32_t>(l);
-  }
-  return n;
+  // boundary labels from the base rows of the predecessors outside A, then
+  // the fixpoint inside A, under the request's raised weights
+  return relabel<K, kDrain, kRaise>(a, r, st, cap_e, n, bd, bn, rse, n_rse, s_ecnt, s_ovf, s_flag);
 }
 
 // seed pass, one thread per request: a request with no tight ignored link
@@ -378,15 +225,7 @@ __global__ __launch_bounds__(256) void whatif_seed_kernel(RepairArgs a) {
     const uint32_t N = a.n_nodes;
     const uint32_t s = a.srcs[r];
     const uint32_t* bd = a.base_dist + static_cast<size_t>(a.base_row[r]) * N;
-    const bool metric = a.use_link_metric != 0;
-    for (uint32_t c = a.cut_ptr[r]; c < a.cut_ptr[r + 1] && !hit; ++c) {
-      const uint4 cut = a.cuts[c];
-      const uint2 rec = a.recs[cut.z];
-      if (rec.x & ORH_REC_SKIP) continue;
-      const uint32_t dx = bd[cut.x];
-      if (dx == kInfD || (cut.x != s && a.ovl[cut.x])) continue;
-      hit = static_cast<uint64_t>(dx) + (metric ? rec.y : 1u) == bd[cut.y];
-    }
+    for (uint32_t c = a.cut_ptr[r]; c < a.cut_ptr[r + 1] && !hit; ++c) hit = cut_tight(a, bd, s, a.cuts[c]);
     if (a.info) a.info[r] = kWhatifTierBase;
   }
   const unsigned long long m = __ballot(hit);

@@ -1631,7 +1631,7 @@ const WhatifKnobs& whatif_knobs() {
   return once;
 }
 
-// One batch of requests of a job, as the three orh_whatif_run* entry points
+// One batch of requests of a job, as the orh_whatif_run* entry points
 // pass it on
 struct WhatifRequests {
   uint32_t n_req;
@@ -1643,6 +1643,9 @@ struct WhatifRequests {
   // nullable (none): per request the metrics it raises (orh_whatif_run_metrics)
   const uint32_t* met_ptr;
   const orh_whatif_metric* mets;
+  // nullable (none): per request the metrics it lowers (orh_whatif_run_lowers)
+  const uint32_t* low_ptr;
+  const orh_whatif_metric* lows;
   uint32_t *d_dist, *d_nh, *d_info;
 };
 
@@ -1655,6 +1658,17 @@ struct StagedRaises {
   std::vector<uint32_t> ptr;  // [n_req + 1] when the batch has a metric list
   std::vector<StagedRaise> list;
   bool any() const { return !list.empty(); }  // else: exactly the run without the lists
+};
+
+// the requests of a batch with at least one effective lower, as the lower pass
+// reads them (orh::LowerArgs): per such request its lowered records and its
+// sorted (record, weight) list of lowers and raises together
+struct StagedLowers {
+  std::vector<uint32_t> req, rec_ptr{0u}, wl_ptr{0u};
+  std::vector<uint4> recs;
+  std::vector<uint2> wl;
+  uint32_t cap_a = 0, cap_e = 0;  // LDS caps of the pass
+  bool any() const { return !req.empty(); }  // else: exactly the run without the list
 };
 
 // the staging's pinned host words and device copy for `words` words, after
@@ -1762,6 +1776,87 @@ int resolve_raises(orh_whatif* job, const WhatifRequests& rq, StagedRaises* out)
   return ORH_OK;
 }
 
+// LDS caps of the lower pass: sized as repair_caps sizes tier 2, with the two
+// frontier bitmaps on top; false when no state fits the LDS
+static bool lower_caps(const orh_ctx* ctx, uint32_t n_nodes, uint32_t* cap_a, uint32_t* cap_e) {
+  const uint32_t ladder[4][2] = {{ctx->rep_cap_a, ctx->rep_cap_e}, {2048, 8192}, {1024, 4096}, {256, 1024}};
+  for (const auto& c : ladder)
+    if (c[0] && orh::lower_lds_bytes(n_nodes, c[0], c[1]) <= ctx->lds_limit) {
+      *cap_a = c[0];
+      *cap_e = c[1];
+      return true;
+    }
+  return false;
+}
+
+// Metric lowers, validated and resolved before anything is queued: per request
+// its effective lowers by record, the smallest of a repeated (link, end) kept,
+// merged with its staged raises into the weight list of the lower pass. A
+// hop-count job checks them and stages none
+int resolve_lowers(orh_whatif* job, const WhatifRequests& rq, const StagedRaises& rs, StagedLowers* out) {
+  if (!rq.low_ptr) return ORH_OK;
+  orh_graph* g = job->g;
+  orh_ctx* ctx = g->ctx;
+  const std::vector<uint32_t>& erow = entry_rows(g);
+  std::vector<uint4> cur;
+  for (uint32_t i = 0; i < rq.n_req; ++i) {
+    cur.clear();
+    for (uint32_t k = rq.low_ptr[i]; k < rq.low_ptr[i + 1]; ++k) {
+      const orh_whatif_metric& ml = rq.lows[k];
+      if (ml.link >= g->n_links) continue;  // as ignore sets do
+      const uint32_t ent[2] = {g->link_ent[2 * static_cast<size_t>(ml.link)],
+                               g->link_ent[2 * static_cast<size_t>(ml.link) + 1]};
+      if (ent[0] == ~0u && ent[1] == ~0u) continue;  // a free slot
+      bool end_ok = ml.from_node == ORH_NO_NODE, down = false;
+      for (uint32_t e : ent)
+        if (e != ~0u) {
+          end_ok |= erow[e] == ml.from_node;
+          down |= (g->meta[e] & ORH_META_DOWN) != 0;
+        }
+      if (!end_ok) return fail(ctx, ORH_E_INVALID, "orh_whatif_run_lowers: from_node is not an end of the link");
+      if (down) continue;  // restoring a down link is a topology change
+      if (ml.metric == 0)
+        return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_run_lowers: what-if jobs have no zero-metric links");
+      auto named = [&](uint32_t e) { return e != ~0u && (ml.from_node == ORH_NO_NODE || erow[e] == ml.from_node); };
+      for (uint32_t e : ent)
+        if (named(e) && ml.metric > g->w_out[e])
+          return fail(ctx, ORH_E_INVALID, "orh_whatif_run_lowers: metric above the current one (a raise goes in h_metrics)");
+      for (uint32_t e : ent) {
+        if (!named(e)) continue;
+        if (rq.met_ptr)
+          for (uint32_t k2 = rq.met_ptr[i]; k2 < rq.met_ptr[i + 1]; ++k2)
+            if (rq.mets[k2].link == ml.link &&
+                (rq.mets[k2].from_node == ORH_NO_NODE || rq.mets[k2].from_node == erow[e]))
+              return fail(ctx, ORH_E_INVALID, "orh_whatif_run_lowers: a (link, end) both raised and lowered in one request");
+        if (ml.metric == g->w_out[e] || !job->use_link_metric) continue;
+        cur.push_back(make_uint4(erow[e], g->col[e], g->pos[e], ml.metric));
+      }
+    }
+    if (cur.empty()) continue;
+    std::sort(cur.begin(), cur.end(), [](const uint4& x, const uint4& y) { return x.z != y.z ? x.z < y.z : x.w < y.w; });
+    cur.erase(std::unique(cur.begin(), cur.end(), [](const uint4& x, const uint4& y) { return x.z == y.z; }), cur.end());
+    out->req.push_back(i);
+    const size_t w0 = out->wl.size();
+    for (const uint4& x : cur) {
+      out->recs.push_back(x);
+      out->wl.push_back(make_uint2(x.z, x.w));
+    }
+    if (rs.any())
+      for (uint32_t k = rs.ptr[i]; k < rs.ptr[i + 1]; ++k) out->wl.push_back(make_uint2(rs.list[k].rec, rs.list[k].w));
+    std::sort(out->wl.begin() + static_cast<ptrdiff_t>(w0), out->wl.end(),
+              [](const uint2& x, const uint2& y) { return x.x < y.x; });
+    out->rec_ptr.push_back(static_cast<uint32_t>(out->recs.size()));
+    out->wl_ptr.push_back(static_cast<uint32_t>(out->wl.size()));
+  }
+  if (!out->any()) return ORH_OK;
+  if (repair_slots_for(g->n_nodes, g->n_recs, rq.n_req) == 0)
+    return fail(ctx, ORH_E_UNSUPPORTED,
+                "orh_whatif_run_lowers: no repair slot fits this graph, and the full search takes no lowers");
+  if (!lower_caps(ctx, g->n_nodes, &out->cap_a, &out->cap_e))
+    return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_run_lowers: the lower pass's state exceeds LDS");
+  return ORH_OK;
+}
+
 // The most cuts the batch stages: two per ignored link, one per out-record of
 // a drained node (an upper bound: the sets are deduplicated, and lose the
 // request's source, while they are staged) and one per raised record
@@ -1787,11 +1882,15 @@ int count_cuts(orh_whatif* job, const WhatifRequests& rq, const StagedRaises& rs
 //   with drains: drn_ptr[n+1] | drn[n_drn] |
 //   cut_ptr[n+1] | (pad to 16 B) cuts uint4[n_cuts] |
 //   with raises: rse_ptr[n+1] | (pad to 8 B) rse uint2[n_rse] |
+//   with lowers (m requests have some): req[m] | rec_ptr[m+1] | wl_ptr[m+1] |
+//     (pad to 16 B) recs uint4[n_lrec] | wl uint2[n_lwl] |
 //   4 spare words
 struct WhatifLayout {
   size_t off_src, off_ip, off_ign, off_dp, off_drn, off_cp, off_cuts, off_rp, off_rse, words;
+  size_t off_lreq, off_lrp, off_lwp, off_lrec, off_lwl;
 };
-WhatifLayout whatif_layout(size_t n, size_t n_ign, bool drains, size_t n_drn, size_t n_cuts, size_t n_rse) {
+WhatifLayout whatif_layout(size_t n, size_t n_ign, bool drains, size_t n_drn, size_t n_cuts, size_t n_rse,
+                           const StagedLowers& sl) {
   WhatifLayout l{};
   l.off_src = n;
   l.off_ip = 2 * n;
@@ -1802,15 +1901,25 @@ WhatifLayout whatif_layout(size_t n, size_t n_ign, bool drains, size_t n_drn, si
   l.off_cuts = (l.off_cp + n + 1 + 3) & ~size_t{3};
   l.off_rp = l.off_cuts + 4 * n_cuts;
   l.off_rse = (l.off_rp + n + 1 + 1) & ~size_t{1};
-  l.words = (n_rse ? l.off_rse + 2 * n_rse : l.off_rp) + 4;
+  size_t end = n_rse ? l.off_rse + 2 * n_rse : l.off_rp;
+  if (sl.any()) {
+    const size_t m = sl.req.size();
+    l.off_lreq = end;
+    l.off_lrp = l.off_lreq + m;
+    l.off_lwp = l.off_lrp + m + 1;
+    l.off_lrec = (l.off_lwp + m + 1 + 3) & ~size_t{3};
+    l.off_lwl = l.off_lrec + 4 * sl.recs.size();
+    end = l.off_lwl + 2 * sl.wl.size();
+  }
+  l.words = end + 4;
   return l;
 }
 
 // The pinned words of a run: per request its ignore set sorted and unique, its
 // drain set likewise and without its own source, and its cuts: ignored link
 // ends, then drained nodes' out-records, then raised records
-void fill_stage(const orh_whatif* job, const WhatifRequests& rq, const StagedRaises& rs, const WhatifLayout& l,
-                uint32_t* h) {
+void fill_stage(const orh_whatif* job, const WhatifRequests& rq, const StagedRaises& rs, const StagedLowers& sl,
+                const WhatifLayout& l, uint32_t* h) {
   orh_graph* g = job->g;
   const uint32_t n_req = rq.n_req;
   std::memcpy(h, rq.src_idx, n_req * 4ull);
@@ -1868,6 +1977,13 @@ void fill_stage(const orh_whatif* job, const WhatifRequests& rq, const StagedRai
     hc[i + 1] = static_cast<uint32_t>(nc);
   }
   if (rs.any()) std::memcpy(h + l.off_rp, rs.ptr.data(), (size_t{n_req} + 1) * 4);
+  if (sl.any()) {  // the lower pass's lists, as resolve_lowers made them
+    std::memcpy(h + l.off_lreq, sl.req.data(), sl.req.size() * 4);
+    std::memcpy(h + l.off_lrp, sl.rec_ptr.data(), sl.rec_ptr.size() * 4);
+    std::memcpy(h + l.off_lwp, sl.wl_ptr.data(), sl.wl_ptr.size() * 4);
+    std::memcpy(h + l.off_lrec, sl.recs.data(), sl.recs.size() * sizeof(uint4));
+    std::memcpy(h + l.off_lwl, sl.wl.data(), sl.wl.size() * sizeof(uint2));
+  }
 }
 
 // what provision_run decided for a run
@@ -1879,6 +1995,8 @@ struct RunPlan {
   // or the job's ORH_WHATIF_SEARCH_LARGE (ORH_WHATIF_SEARCH_CAP per run). A
   // run with raises takes none (the search knows no raised weights): its slot
   // tier ends every request
+  // run with lowers neither (a lower leaves the metric range the search's
+  // bucket widths are planned from)
   uint32_t full_n;
   bool split;           // the slot tier on its own stream, over the run slot's memory
   uint32_t full_cap;    // of full_n, what the labels' 1 GB and the batch allow
@@ -1901,13 +2019,14 @@ int regrow(orh_ctx* ctx, void** p, size_t* cap, size_t bytes) {
 
 // Work queues, slot memory and full-search labels of the run in slot c, each
 // grown to the exact need, after the wait that makes freeing the old one safe
-int provision_run(orh_whatif* job, int c, uint32_t n_req, bool raises, RunPlan* out) {
+int provision_run(orh_whatif* job, int c, uint32_t n_req, bool raises, uint32_t n_low, RunPlan* out) {
   orh_graph* g = job->g;
   orh_ctx* ctx = g->ctx;
   RunSlot& slot = job->run[c];
   const uint32_t N = g->n_nodes;
   const WhatifKnobs& knobs = whatif_knobs();
-  const size_t work = 3 * size_t{n_req} + orh::kWhatifCounters + n_req;
+  // the lower pass's slot queue (one word per request that lowers) at the end
+  const size_t work = 3 * size_t{n_req} + orh::kWhatifCounters + n_req + n_low;
   if (work * 4 > slot.work_cap) {
     if (slot.pending) ORH_HIP(ctx, hipStreamSynchronize(job->side));  // its old buffer may be in use
     const int rc = regrow(ctx, reinterpret_cast<void**>(&slot.d_work), &slot.work_cap, work * 4);
@@ -2008,6 +2127,25 @@ orh::RepairArgs fill_repair_args(const orh_whatif* job, int c, const WhatifLayou
   return ra;
 }
 
+// the lower pass over the run's staged requests (n_low 0: the run has none)
+orh::LowerArgs fill_lower_args(const orh_whatif* job, int c, const WhatifLayout& l, const StagedLowers& sl,
+                               uint32_t n_req) {
+  orh::LowerArgs la{};
+  if (!sl.any()) return la;
+  const RunSlot& slot = job->run[c];
+  const uint32_t* d = slot.stage.d;
+  la.n_low = static_cast<uint32_t>(sl.req.size());
+  la.req = d + l.off_lreq;
+  la.rec_ptr = d + l.off_lrp;
+  la.recs = reinterpret_cast<const uint4*>(d + l.off_lrec);
+  la.wl_ptr = d + l.off_lwp;
+  la.wl = reinterpret_cast<const uint2*>(d + l.off_lwl);
+  la.queue = slot.d_work + 3 * size_t{n_req} + orh::kWhatifCounters + n_req;
+  la.cap_a = sl.cap_a;
+  la.cap_e = sl.cap_e;
+  return la;
+}
+
 // The full search (spf_global_nh_async_kernel) over the run's staged requests.
 // With slots it takes the first entries of the slot tier's queue: workgroup b
 // searches request queue[b] while b < the queue's length. Without, the
@@ -2048,8 +2186,10 @@ orh::SpfArgs full_search_args(const orh_whatif* job, const orh::RepairArgs& ra) 
 
 // Seed and copy on the context stream; the repair tiers on `side` behind
 // them, the slot tier of a split run on its t3 stream; then the full search
-// on `side`. side_ev marks the end of the run's side part
-int launch_run(orh_whatif* job, int c, const orh::RepairArgs& ra, const RunPlan& p) {
+// on `side`; then the lower pass (stage 2 of the requests that lower metrics)
+// behind the run's last tier, on that tier's stream. side_ev marks the end of
+// the run's side part
+int launch_run(orh_whatif* job, int c, const orh::RepairArgs& ra, const orh::LowerArgs& la, const RunPlan& p) {
   orh_graph* g = job->g;
   orh_ctx* ctx = g->ctx;
   RunSlot& slot = job->run[c];
@@ -2075,6 +2215,10 @@ int launch_run(orh_whatif* job, int c, const orh::RepairArgs& ra, const RunPlan&
     if (e != hipSuccess)
       return hip_fail(ctx, e, p.n_slots ? "what-if full-search launch" : "what-if fallback launch");
   }
+  if (la.n_low) {
+    e = orh::launch_lower(ra, la, g->ell_k, ctx->lds_limit, p.split ? t3s : job->side);
+    if (e != hipSuccess) return hip_fail(ctx, e, "what-if lower launch");
+  }
   // the run's side part ends with its slot tier (its t3 stream, ordered after
   // tiers 1 and 2 through mid_ev) or on `side`
   ORH_HIP(ctx, hipEventRecord(slot.side_ev, p.split ? t3s : job->side));
@@ -2091,12 +2235,14 @@ int whatif_run(orh_whatif* job, const WhatifRequests& rq) {
   orh_ctx* ctx = g->ctx;
   const uint32_t n_req = rq.n_req;
   StagedRaises rs;
+  StagedLowers sl;
   size_t n_cuts = 0;
   int rc = resolve_raises(job, rq, &rs);
+  if (!rc) rc = resolve_lowers(job, rq, rs, &sl);
   if (!rc) rc = count_cuts(job, rq, rs, &n_cuts);
   if (rc) return rc;
   const WhatifLayout lay = whatif_layout(n_req, rq.ign_ptr[n_req], rq.drn_ptr != nullptr,
-                                         rq.drn_ptr ? rq.drn_ptr[n_req] : 0u, n_cuts, rs.list.size());
+                                         rq.drn_ptr ? rq.drn_ptr[n_req] : 0u, n_cuts, rs.list.size(), sl);
   // slot `cur` is reused: its previous run's side part must be done (the
   // context stream waits); so must the other slots' when they write rows this
   // run overwrites
@@ -2106,15 +2252,16 @@ int whatif_run(orh_whatif* job, const WhatifRequests& rq) {
   rc = join_overlapping(job, out, c);
   if (!rc) rc = stage_acquire(ctx, &slot.stage, lay.words);
   if (rc) return rc;
-  fill_stage(job, rq, rs, lay, slot.stage.h);
+  fill_stage(job, rq, rs, sl, lay, slot.stage.h);
   job->cur = (c + 1) % kRunSlots;
   ORH_HIP(ctx, hipMemcpyAsync(slot.stage.d, slot.stage.h, lay.words * 4, hipMemcpyHostToDevice, ctx->stream));
   ORH_HIP(ctx, hipEventRecord(slot.stage.ev, ctx->stream));
   RunPlan plan{};
-  rc = provision_run(job, c, n_req, rs.any(), &plan);
+  // neither raises nor lowers go to a full search
+  rc = provision_run(job, c, n_req, rs.any() || sl.any(), static_cast<uint32_t>(sl.req.size()), &plan);
   if (rc) return rc;
   const orh::RepairArgs ra = fill_repair_args(job, c, lay, plan, rq, rs.any());
-  rc = launch_run(job, c, ra, plan);
+  rc = launch_run(job, c, ra, fill_lower_args(job, c, lay, sl, n_req), plan);
   if (rc) return rc;
   slot.pending = true;
   slot.out_lo = out.lo;
@@ -2301,7 +2448,7 @@ int run_repair(orh_graph* g, const orh_spf_request* req, uint32_t* d_dist, uint3
   if (rc) return rc;
   ORH_HIP(ctx, hipEventRecord(ctx->evm, ctx->stream));
   rc = whatif_run(job, WhatifRequests{n_src, base_row.data(), req->h_ignore_ptr, req->h_ignore_links, nullptr, nullptr,
-                                      nullptr, nullptr, d_dist, d_nh, nullptr});
+                                      nullptr, nullptr, nullptr, nullptr, d_dist, d_nh, nullptr});
   if (!rc) rc = whatif_flush(job);
   if (rc) {
     orh_whatif_destroy(job);
@@ -2339,8 +2486,8 @@ static int checked_run(orh_whatif* job, const WhatifRequests& rq, const char* fn
   const uint32_t n = rq.n_req;
   if (n == 0) return ORH_OK;
   if (!rq.src_idx || !rq.ign_ptr || (rq.ign_ptr[n] && !rq.ign_links) ||
-      (rq.drn_ptr && rq.drn_ptr[n] && !rq.drn_nodes) || (rq.met_ptr && rq.met_ptr[n] && !rq.mets) || !rq.d_dist ||
-      !rq.d_nh)
+      (rq.drn_ptr && rq.drn_ptr[n] && !rq.drn_nodes) || (rq.met_ptr && rq.met_ptr[n] && !rq.mets) ||
+      (rq.low_ptr && rq.low_ptr[n] && !rq.lows) || !rq.d_dist || !rq.d_nh)
     return fail(ctx, ORH_E_INVALID, std::string(fn) + ": null argument");
   if (job->gen != job->g->gen)
     return fail(ctx, ORH_E_STATE, std::string(fn) + ": the graph changed since the job was created");
@@ -2351,7 +2498,7 @@ static int checked_run(orh_whatif* job, const WhatifRequests& rq, const char* fn
 int orh_whatif_run(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
                    const uint32_t* h_ignore_links, uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info) {
   return checked_run(job, WhatifRequests{n_req, h_src_idx, h_ignore_ptr, h_ignore_links, nullptr, nullptr, nullptr,
-                                         nullptr, d_dist, d_nh, d_info},
+                                         nullptr, nullptr, nullptr, d_dist, d_nh, d_info},
                      "orh_whatif_run");
 }
 
@@ -2359,7 +2506,7 @@ int orh_whatif_run_drains(orh_whatif* job, uint32_t n_req, const uint32_t* h_src
                           const uint32_t* h_ignore_links, const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
                           uint32_t* d_dist, uint32_t* d_nh, uint32_t* d_info) {
   return checked_run(job, WhatifRequests{n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes,
-                                         nullptr, nullptr, d_dist, d_nh, d_info},
+                                         nullptr, nullptr, nullptr, nullptr, d_dist, d_nh, d_info},
                      "orh_whatif_run_drains");
 }
 
@@ -2368,8 +2515,18 @@ int orh_whatif_run_metrics(orh_whatif* job, uint32_t n_req, const uint32_t* h_sr
                            const uint32_t* h_metric_ptr, const orh_whatif_metric* h_metrics, uint32_t* d_dist,
                            uint32_t* d_nh, uint32_t* d_info) {
   return checked_run(job, WhatifRequests{n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes,
-                                         h_metric_ptr, h_metrics, d_dist, d_nh, d_info},
+                                         h_metric_ptr, h_metrics, nullptr, nullptr, d_dist, d_nh, d_info},
                      "orh_whatif_run_metrics");
+}
+
+int orh_whatif_run_lowers(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* h_ignore_ptr,
+                          const uint32_t* h_ignore_links, const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
+                          const uint32_t* h_metric_ptr, const orh_whatif_metric* h_metrics,
+                          const uint32_t* h_lower_ptr, const orh_whatif_metric* h_lowers, uint32_t* d_dist,
+                          uint32_t* d_nh, uint32_t* d_info) {
+  return checked_run(job, WhatifRequests{n_req, h_src_idx, h_ignore_ptr, h_ignore_links, h_drain_ptr, h_drain_nodes,
+                                         h_metric_ptr, h_metrics, h_lower_ptr, h_lowers, d_dist, d_nh, d_info},
+                     "orh_whatif_run_lowers");
 }
 
 

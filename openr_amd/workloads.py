@@ -176,6 +176,35 @@ def c4_costout_job(links, adj_dbs, node_names: List[str], n_links: int = C4_WHAT
     return srcs, idx, ignore, metric
 
 
+def c4_costin_job(links, adj_dbs, node_names: List[str], n_links: int = C4_WHATIF_LINKS,
+                  n_srcs: int = C4_WHATIF_SRCS, factor: int = 10, seed: int = C4_SEED):
+    """The cost-in twin of c4_costout_job: the link job's links are costed
+    out (both ends' metrics x factor) in the graph itself, and request (link,
+    source) asks "what changes if this link is costed back in?" by lowering
+    both ends to their plain values. links, adj_dbs as for c4_costout_job (the
+    plain graph). Returns (the costed-out adjacency databases to load - same
+    structure, so the same link ids -, sources, per request its source index,
+    per request its (empty) ignore set, per request its lowers [(link id, end
+    name, plain metric)] - one per end)."""
+    import dataclasses
+    desc = dict(links)
+    srcs, idx, sets = c4_what_if_job([lid for lid, _ in links], node_names, n_links, n_srcs, seed)
+    cur = {(db.thisNodeName, a.ifName): a.metric for db in adj_dbs for a in db.adjacencies}
+    costed = set()
+    for lid in {l for (l,) in sets}:
+        n1, if1, n2, if2 = desc[lid]
+        costed.update(((n1, if1), (n2, if2)))
+    dbs = [dataclasses.replace(db, adjacencies=[
+        dataclasses.replace(a, metric=a.metric * factor) if (db.thisNodeName, a.ifName) in costed else a
+        for a in db.adjacencies]) for db in adj_dbs]
+    ignore = [[] for _ in sets]
+    lower = []
+    for (lid,) in sets:
+        n1, if1, n2, if2 = desc[lid]
+        lower.append([(lid, n1, cur[(n1, if1)]), (lid, n2, cur[(n2, if2)])])
+    return dbs, srcs, idx, ignore, lower
+
+
 def c4_node_weights(node_names: List[str], seed: int = C4_SEED, max_prefixes: int = 64):
     """Seeded per-node weights for what-if impact summaries on the C4 WAN: the
     prefixes each node advertises, uniform in [0, max_prefixes], as
