@@ -464,7 +464,7 @@ int orh_whatif_run_metrics(orh_whatif* job, uint32_t n_req, const uint32_t* h_sr
  *   the base row".
  * - orh_whatif_impact's classes assume that no node is nearer than in the
  *   base row: rows of a request with an effective lower are outside its
- *   contract (a "gain" summary does not exist yet). */
+ *   contract. orh_whatif_gain summarises them (and any other run's rows). */
 int orh_whatif_run_lowers(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx,
                           const uint32_t* h_ignore_ptr, const uint32_t* h_ignore_links,
                           const uint32_t* h_drain_ptr, const uint32_t* h_drain_nodes,
@@ -508,7 +508,7 @@ int orh_whatif_flush(orh_whatif* job);
  * buffer (a job's rows are far too many to copy out: C4 is 105 GB).
  * Request i's row (d_dist + i*N, d_nh + i*N, one mask word per node: the rows
  * an orh_whatif_run / _run_drains / _run_metrics of this job wrote; rows of a
- * request with an effective lower are outside the contract) is compared with the
+ * request with an effective lower belong to orh_whatif_gain) is compared with the
  * job's base row of source h_src_idx[i] (orh_whatif_base_rows), node by node.
  * A node unreached in the base row is in no class, and neither is the
  * request's source. */
@@ -558,6 +558,50 @@ typedef struct orh_whatif_impact_opts { /* zero-initialise; every field nullable
 int orh_whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* d_dist,
                       const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_impact_opts* opts,
                       orh_whatif_impact_rec* d_out);
+/* Two-sided summaries: orh_whatif_impact for rows in which a node may also be
+ * nearer than in the base row, which is what a metric lower does
+ * (orh_whatif_run_lowers). Rows of any run of this job qualify. Per node v,
+ * with bd / rd its distance in the base row / the request's row (a node
+ * unreached in the base row, and the request's source, are in no class):
+ *   lost      unreached in the request's row
+ *   farther   reached in both, rd > bd
+ *   nearer    reached in both, rd < bd
+ *   rehomed   reached in both, rd == bd, first-hop masks differ
+ *   narrowed  reached in both, popcount(mask) smaller than in the base row
+ *   widened   reached in both, popcount(mask) larger than in the base row
+ * narrowed and widened are counted whatever the distance did (a node that
+ * gains an ECMP path at the same distance is rehomed and widened). "moved" is
+ * lost, farther, nearer or rehomed. On rows without a nearer node the nine
+ * fields shared with orh_whatif_impact_rec hold the same values. */
+typedef struct orh_whatif_gain_rec { /* 80 bytes, 8-byte aligned */
+  uint32_t lost, farther, nearer, rehomed, narrowed, widened;
+  uint32_t max_stretch;   /* max over `farther` of rd - bd, 0 if none */
+  uint32_t worst_node;    /* the node with that stretch, the smallest id on a tie;
+                             ORH_NO_NODE if farther == 0 */
+  uint32_t max_gain;      /* max over `nearer` of bd - rd, 0 if none */
+  uint32_t best_node;     /* the node with that gain, the smallest id on a tie;
+                             ORH_NO_NODE if nearer == 0 */
+  uint64_t sum_stretch;   /* sum over `farther` of rd - bd */
+  uint64_t sum_gain;      /* sum over `nearer` of bd - rd */
+  uint64_t lost_weight;   /* sum of weight[v] over `lost` (0 without weights) */
+  uint64_t moved_weight;  /* sum of weight[v] over lost + farther + nearer + rehomed */
+  uint64_t nearer_weight; /* sum of weight[v] over `nearer` */
+} orh_whatif_gain_rec;
+typedef struct orh_whatif_gain_opts { /* zero-initialise; every field nullable */
+  const uint32_t* d_weight; /* [N] per-node weight */
+  uint32_t* d_node_lost;    /* [N] += 1 per request in which the node is lost */
+  uint32_t* d_node_moved;   /* [N] += 1 per request in which it is moved */
+  uint32_t* d_node_nearer;  /* [N] += 1 per request in which it is nearer */
+} orh_whatif_gain_opts;
+/* d_out [n_req] records (device). Ordering, d_info and the tier-0 skip,
+ * ORH_WHATIF_SHARE_BASE, the graph without tier-3 slots, validation and its
+ * codes, the accumulating node arrays and the reuse of h_src_idx are exactly
+ * orh_whatif_impact's. Tier 0 means "equal to the base row" for a run with
+ * lowers as well (orh_whatif_run_lowers), so a tier-0 request's record is all
+ * zeros with worst_node = best_node = ORH_NO_NODE and its row is NOT read. */
+int orh_whatif_gain(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* d_dist,
+                    const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_gain_opts* opts,
+                    orh_whatif_gain_rec* d_out);
 /* device time from the job's creation (base searches) to the end of its last
  * run (flushes; HIP events; waits for that run) */
 int orh_whatif_elapsed_ms(orh_whatif* job, double* ms_out);

@@ -28,7 +28,8 @@ HIP_SRCS = [os.path.join(CSRC, "orh_api.hip")] + [
     os.path.join(CSRC, "kernels", f + ".hip")
     for f in ("spf_msbfs_kernels", "spf_lds_kernels", "spf_wms_kernels", "spf_bfs_kernels",
               "spf_hop_kernels", "spf_hbm_kernels", "spf_dist_kernels", "spf_exact_kernels", "spf_plan",
-              "route_kernels", "whatif_kernels", "whatif_lower_kernels", "whatif_impact_kernels", "ksp_kernels")]
+              "route_kernels", "whatif_kernels", "whatif_lower_kernels", "whatif_impact_kernels", "whatif_gain_kernels",
+              "ksp_kernels")]
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("link_state.cpp", "prefix_state.cpp", "spf_solver.cpp",
                                                    "rib_policy.cpp", "thrift_compact.cpp",
                                                    "decision_ingest.cpp", "multi_device.cpp", "whatif_batch.cpp",

@@ -688,6 +688,50 @@ py::tuple nodeImpactArrays(const Job& b, size_t n) {
   return py::make_tuple(lost, moved);
 }
 
+// the records as a dict of arrays keyed by orh_whatif_gain_rec's field names
+template <class Job>
+py::dict gainDict(const Job& b, size_t n) {
+  std::vector<orh_whatif_gain_rec> rec(n);
+  b.gain(rec.data());
+  py::dict d;
+  auto col32 = [&](const char* name, uint32_t orh_whatif_gain_rec::*f) {
+    py::array_t<uint32_t> a(n);
+    for (size_t i = 0; i < n; ++i) a.mutable_data()[i] = rec[i].*f;
+    d[name] = a;
+  };
+  auto col64 = [&](const char* name, uint64_t orh_whatif_gain_rec::*f) {
+    py::array_t<uint64_t> a(n);
+    for (size_t i = 0; i < n; ++i) a.mutable_data()[i] = rec[i].*f;
+    d[name] = a;
+  };
+  col32("lost", &orh_whatif_gain_rec::lost);
+  col32("farther", &orh_whatif_gain_rec::farther);
+  col32("nearer", &orh_whatif_gain_rec::nearer);
+  col32("rehomed", &orh_whatif_gain_rec::rehomed);
+  col32("narrowed", &orh_whatif_gain_rec::narrowed);
+  col32("widened", &orh_whatif_gain_rec::widened);
+  col32("max_stretch", &orh_whatif_gain_rec::max_stretch);
+  col32("worst_node", &orh_whatif_gain_rec::worst_node);
+  col32("max_gain", &orh_whatif_gain_rec::max_gain);
+  col32("best_node", &orh_whatif_gain_rec::best_node);
+  col64("sum_stretch", &orh_whatif_gain_rec::sum_stretch);
+  col64("sum_gain", &orh_whatif_gain_rec::sum_gain);
+  col64("lost_weight", &orh_whatif_gain_rec::lost_weight);
+  col64("moved_weight", &orh_whatif_gain_rec::moved_weight);
+  col64("nearer_weight", &orh_whatif_gain_rec::nearer_weight);
+  return d;
+}
+
+template <class Job>
+py::tuple nodeGainArrays(const Job& b, size_t n) {
+  py::array_t<uint32_t> lost(n), moved(n), nearer(n);
+  std::fill_n(lost.mutable_data(), n, 0u);
+  std::fill_n(moved.mutable_data(), n, 0u);
+  std::fill_n(nearer.mutable_data(), n, 0u);
+  b.nodeGain(lost.mutable_data(), moved.mutable_data(), nearer.mutable_data());
+  return py::make_tuple(lost, moved, nearer);
+}
+
 // what_if_batch(metric=... / lower=...): per request a list of (link_id, from_name or
 // None for both ends, new_metric)
 using PyMetricRaises = std::vector<std::vector<std::tuple<uint32_t, std::optional<std::string>, uint32_t>>>;
@@ -1199,6 +1243,13 @@ PYBIND11_MODULE(_openr_host, m) {
            py::arg("on") = true, py::arg("weights") = py::none(), py::arg("node_counts") = false)
       .def("impact", [](const WhatIfBatch& b) { return impactDict(b, b.requests()); })
       .def("node_impact", [](const WhatIfBatch& b) { return nodeImpactArrays(b, b.nodes()); })
+      .def("set_gain",
+           [](WhatIfBatch& b, bool on, const py::object& weights, bool nodeCounts) {
+             b.setGain(on, weightPairs(weights), nodeCounts);
+           },
+           py::arg("on") = true, py::arg("weights") = py::none(), py::arg("node_counts") = false)
+      .def("gain", [](const WhatIfBatch& b) { return gainDict(b, b.requests()); })
+      .def("node_gain", [](const WhatIfBatch& b) { return nodeGainArrays(b, b.nodes()); })
       .def_property_readonly("requests", &WhatIfBatch::requests)
       .def_property_readonly("chunk", &WhatIfBatch::chunk)
       .def_property_readonly("nodes", &WhatIfBatch::nodes)
@@ -1234,7 +1285,14 @@ PYBIND11_MODULE(_openr_host, m) {
            },
            py::arg("on") = true, py::arg("weights") = py::none(), py::arg("node_counts") = false)
       .def("impact", [](const MultiDeviceWhatIf& b) { return impactDict(b, b.requests()); })
-      .def("node_impact", [](const MultiDeviceWhatIf& b) { return nodeImpactArrays(b, b.nodes()); });
+      .def("node_impact", [](const MultiDeviceWhatIf& b) { return nodeImpactArrays(b, b.nodes()); })
+      .def("set_gain",
+           [](MultiDeviceWhatIf& b, bool on, const py::object& weights, bool nodeCounts) {
+             b.setGain(on, weightPairs(weights), nodeCounts);
+           },
+           py::arg("on") = true, py::arg("weights") = py::none(), py::arg("node_counts") = false)
+      .def("gain", [](const MultiDeviceWhatIf& b) { return gainDict(b, b.requests()); })
+      .def("node_gain", [](const MultiDeviceWhatIf& b) { return nodeGainArrays(b, b.nodes()); });
   py::class_<MultiDeviceKthPaths>(m, "MultiDeviceKthPaths")
       .def("run", &MultiDeviceKthPaths::run, py::call_guard<py::gil_scoped_release>())
       .def("run_block", &MultiDeviceKthPaths::runBlock, py::arg("block"))

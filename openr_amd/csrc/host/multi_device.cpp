@@ -386,6 +386,41 @@ void MultiDeviceWhatIf::nodeImpact(uint32_t* lost, uint32_t* moved) const {
   }
 }
 
+void MultiDeviceWhatIf::setGain(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights,
+                                bool nodeCounts) {
+  for (auto& b : blocks_)
+    if (b.job) b.job->setGain(on, weights, nodeCounts);
+}
+
+void MultiDeviceWhatIf::gain(orh_whatif_gain_rec* out) const {
+  std::vector<orh_whatif_gain_rec> tmp;
+  for (const auto& b : blocks_) {
+    if (!b.job) continue;
+    tmp.resize(b.reqs.size());
+    b.job->gain(tmp.data());
+    for (size_t k = 0; k < b.reqs.size(); ++k) out[b.reqs[k]] = tmp[k];
+  }
+}
+
+void MultiDeviceWhatIf::nodeGain(uint32_t* lost, uint32_t* moved, uint32_t* nearer) const {
+  std::vector<uint32_t> l, m, g;
+  bool first = true;
+  for (const auto& b : blocks_) {
+    if (!b.job) continue;
+    const size_t n = b.job->nodes();
+    l.resize(n);
+    m.resize(n);
+    g.resize(n);
+    b.job->nodeGain(l.data(), m.data(), g.data());
+    for (size_t v = 0; v < n; ++v) {
+      lost[v] = (first ? 0u : lost[v]) + l[v];
+      moved[v] = (first ? 0u : moved[v]) + m[v];
+      nearer[v] = (first ? 0u : nearer[v]) + g[v];
+    }
+    first = false;
+  }
+}
+
 // ---- MultiDeviceKthPaths -----------------------------------------------------
 MultiDeviceKthPaths::MultiDeviceKthPaths(const ReplicatedLinkState& rls,
                                          const std::vector<std::pair<std::string, std::string>>& pairs)

@@ -150,6 +150,10 @@ class MultiDeviceWhatIf {
                  bool nodeCounts = false);
   void impact(orh_whatif_impact_rec* out) const;            // [requests()]
   void nodeImpact(uint32_t* lost, uint32_t* moved) const;  // [nodes] each
+  // gain summaries (WhatIfBatch::setGain) on every block, likewise
+  void setGain(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights = {}, bool nodeCounts = false);
+  void gain(orh_whatif_gain_rec* out) const;                                // [requests()]
+  void nodeGain(uint32_t* lost, uint32_t* moved, uint32_t* nearer) const;  // [nodes] each
 
  private:
   struct Block {

@@ -133,8 +133,11 @@ void WhatIfBatch::freeImpact() {
   if (dWeight_) orh_device_free(ctx_, dWeight_);
   if (dNodeLost_) orh_device_free(ctx_, dNodeLost_);
   if (dNodeMoved_) orh_device_free(ctx_, dNodeMoved_);
+  if (dGain_) orh_device_free(ctx_, dGain_);
+  if (dNodeNearer_) orh_device_free(ctx_, dNodeNearer_);
   dImpact_ = nullptr;
-  dWeight_ = dNodeLost_ = dNodeMoved_ = nullptr;
+  dGain_ = nullptr;
+  dWeight_ = dNodeLost_ = dNodeMoved_ = dNodeNearer_ = nullptr;
 }
 
 void WhatIfBatch::release() {
@@ -145,6 +148,16 @@ void WhatIfBatch::release() {
       hNodeLost_.resize(n_);
       hNodeMoved_.resize(n_);
       nodeImpact(hNodeLost_.data(), hNodeMoved_.data());
+    }
+  }
+  if (gainRan_ && dGain_) {
+    hGain_.resize(srcIdx_.size());
+    gain(hGain_.data());
+    if (nodeCounts_ && dNodeNearer_) {
+      hNodeLost_.resize(n_);
+      hNodeMoved_.resize(n_);
+      hNodeNearer_.resize(n_);
+      nodeGain(hNodeLost_.data(), hNodeMoved_.data(), hNodeNearer_.data());
     }
   }
   freeImpact();
@@ -161,7 +174,7 @@ void WhatIfBatch::release() {
 }
 
 WhatIfBatch::~WhatIfBatch() {
-  impactRan_ = false;  // nothing to keep
+  impactRan_ = gainRan_ = false;  // nothing to keep
   release();
   if (dInfo_) orh_device_free(ctx_, dInfo_);
   if (dDigest_) orh_device_free(ctx_, dDigest_);
@@ -179,6 +192,22 @@ void WhatIfBatch::setDigests(bool on) {
 
 void WhatIfBatch::setImpact(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights,
                             bool nodeCounts) {
+  setSummary(&impact_, gain_, on, weights, nodeCounts);
+}
+
+void WhatIfBatch::setGain(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights, bool nodeCounts) {
+  setSummary(&gain_, impact_, on, weights, nodeCounts);
+}
+
+// one summary mode switched on or off; the weights and the node-count flag
+// belong to whichever mode is on, so switching one off leaves them alone while
+// the other is on
+void WhatIfBatch::setSummary(bool* mode, bool other, bool on,
+                             const std::vector<std::pair<std::string, uint32_t>>& weights, bool nodeCounts) {
+  if (!on && other) {
+    *mode = false;
+    return;
+  }
   std::vector<uint32_t> w;
   if (on && !weights.empty()) {
     w.assign(n_, 0u);
@@ -188,7 +217,7 @@ void WhatIfBatch::setImpact(bool on, const std::vector<std::pair<std::string, ui
       w[*id] = x;
     }
   }
-  impact_ = on;
+  *mode = on;
   nodeCounts_ = on && nodeCounts;
   weights_ = std::move(w);
   if (dWeight_) {  // the next run uploads the new ones
@@ -201,6 +230,18 @@ void WhatIfBatch::setImpact(bool on, const std::vector<std::pair<std::string, ui
 void WhatIfBatch::queueImpact(size_t c) {
   const Chunk& ch = chunks_[c];
   const int b = static_cast<int>(c % nBuf_);
+  if (gain_) {
+    orh_whatif_gain_opts opts{};
+    opts.d_weight = weights_.empty() ? nullptr : dWeight_;
+    opts.d_node_lost = nodeCounts_ ? dNodeLost_ : nullptr;
+    opts.d_node_moved = nodeCounts_ ? dNodeMoved_ : nullptr;
+    opts.d_node_nearer = nodeCounts_ ? dNodeNearer_ : nullptr;
+    check(ctx_,
+          orh_whatif_gain(job_, static_cast<uint32_t>(ch.hi - ch.lo), srcIdx_.data() + ch.lo, dDist_[b], dNh_[b],
+                          dInfo_ + ch.lo, &opts, dGain_ + ch.lo),
+          "orh_whatif_gain");
+    return;
+  }
   orh_whatif_impact_opts opts{};
   opts.d_weight = weights_.empty() ? nullptr : dWeight_;
   opts.d_node_lost = nodeCounts_ ? dNodeLost_ : nullptr;
@@ -232,16 +273,42 @@ void WhatIfBatch::nodeImpact(uint32_t* lost, uint32_t* moved) const {
   }
 }
 
+void WhatIfBatch::gain(orh_whatif_gain_rec* out) const {
+  if (!gainRan_) throw std::logic_error("WhatIfBatch: gain was not enabled for the last run");
+  if (dGain_)
+    check(ctx_, orh_memcpy_d2h(ctx_, out, dGain_, srcIdx_.size() * sizeof(orh_whatif_gain_rec)), "orh_memcpy_d2h");
+  else
+    std::copy(hGain_.begin(), hGain_.end(), out);
+}
+
+void WhatIfBatch::nodeGain(uint32_t* lost, uint32_t* moved, uint32_t* nearer) const {
+  if (!gainRan_ || !nodeCounts_)
+    throw std::logic_error("WhatIfBatch: node counts were not enabled for the last run");
+  if (dNodeNearer_) {
+    check(ctx_, orh_memcpy_d2h(ctx_, lost, dNodeLost_, n_ * 4ull), "orh_memcpy_d2h");
+    check(ctx_, orh_memcpy_d2h(ctx_, moved, dNodeMoved_, n_ * 4ull), "orh_memcpy_d2h");
+    check(ctx_, orh_memcpy_d2h(ctx_, nearer, dNodeNearer_, n_ * 4ull), "orh_memcpy_d2h");
+  } else {
+    std::copy(hNodeLost_.begin(), hNodeLost_.end(), lost);
+    std::copy(hNodeMoved_.begin(), hNodeMoved_.end(), moved);
+    std::copy(hNodeNearer_.begin(), hNodeNearer_.end(), nearer);
+  }
+}
+
 void WhatIfBatch::run() {
-  impactRan_ = false;
+  impactRan_ = gainRan_ = false;
+  if (impact_ && gain_)
+    throw std::invalid_argument("WhatIfBatch: impact and gain summaries are two modes of one pass, enable one");
   if (impact_ && lowers_)  // the summary's classes assume that no node gets nearer
-    throw std::invalid_argument("WhatIfBatch: impact summaries do not cover requests that lower metrics");
-  if (impact_) {  // buffers of the mode; the node counters start at zero (before the job's clock)
+    throw std::invalid_argument(
+        "WhatIfBatch: impact summaries do not cover requests that lower metrics (gain summaries do: setGain)");
+  if (impact_ || gain_) {  // buffers of the mode; the node counters start at zero (before the job's clock)
     auto alloc = [&](auto** p, size_t bytes) {
       if (!*p) check(ctx_, orh_device_alloc(ctx_, std::max<size_t>(bytes, 8), reinterpret_cast<void**>(p)),
                      "orh_device_alloc");
     };
-    alloc(&dImpact_, srcIdx_.size() * sizeof(orh_whatif_impact_rec));
+    if (impact_) alloc(&dImpact_, srcIdx_.size() * sizeof(orh_whatif_impact_rec));
+    else alloc(&dGain_, srcIdx_.size() * sizeof(orh_whatif_gain_rec));
     if (!weights_.empty() && !dWeight_) {
       alloc(&dWeight_, n_ * 4ull);
       check(ctx_, orh_memcpy_h2d(ctx_, dWeight_, weights_.data(), n_ * 4ull), "orh_memcpy_h2d");
@@ -252,6 +319,10 @@ void WhatIfBatch::run() {
       const std::vector<uint32_t> zero(n_, 0u);
       check(ctx_, orh_memcpy_h2d(ctx_, dNodeLost_, zero.data(), n_ * 4ull), "orh_memcpy_h2d");
       check(ctx_, orh_memcpy_h2d(ctx_, dNodeMoved_, zero.data(), n_ * 4ull), "orh_memcpy_h2d");
+      if (gain_) {
+        alloc(&dNodeNearer_, n_ * 4ull);
+        check(ctx_, orh_memcpy_h2d(ctx_, dNodeNearer_, zero.data(), n_ * 4ull), "orh_memcpy_h2d");
+      }
     }
   }
   // the graph as it is now: a what-if job is bound to its graph's structure
@@ -291,7 +362,7 @@ void WhatIfBatch::run() {
     const int b = static_cast<int>(c % nBuf_);  // cycle the row buffers
     // this run overwrites the rows of chunk c - nBuf_, and waits for them by
     // itself: their summary goes right before it
-    if (impact_ && c >= static_cast<size_t>(nBuf_)) queueImpact(c - nBuf_);
+    if ((impact_ || gain_) && c >= static_cast<size_t>(nBuf_)) queueImpact(c - nBuf_);
     if (lowers_)
       check(ctx_,
             orh_whatif_run_lowers(job_, nr, srcIdx_.data() + ch.lo, ch.ptr.data(), ch.links.data(),
@@ -320,10 +391,10 @@ void WhatIfBatch::run() {
       check(ctx_, orh_row_digest(ctx_, dDist_[b], dNh_[b], 1, n_, nr, dDigest_ + ch.lo), "orh_row_digest");
     }
   }
-  if (impact_) {  // the chunks still in the buffers
+  if (impact_ || gain_) {  // the chunks still in the buffers
     const size_t nc = chunks_.size();
     for (size_t c = nc > static_cast<size_t>(nBuf_) ? nc - nBuf_ : 0; c < nc; ++c) queueImpact(c);
-    impactRan_ = true;
+    (gain_ ? gainRan_ : impactRan_) = true;
   }
   check(ctx_, orh_whatif_flush(job_), "orh_whatif_flush");
 }

@@ -51,7 +51,7 @@ class WhatIfBatch {
   // orh_whatif_run_metrics). lower: per request its metric lowers, same
   // conventions (an increase fails the run, see orh_whatif_run_lowers); a
   // batch with lowers takes no impact summaries (run() throws
-  // std::invalid_argument with setImpact(true))
+  // std::invalid_argument with setImpact(true)): setGain summarises it
   WhatIfBatch(const LinkState& ls, const std::vector<std::string>& srcs, const std::vector<uint32_t>& srcIdx,
               const std::vector<std::vector<uint32_t>>& ignore, uint32_t chunk, bool useLinkMetric = true,
               bool shareBase = false, bool searchLarge = false,
@@ -91,6 +91,16 @@ class WhatIfBatch {
   void impact(orh_whatif_impact_rec* out) const;
   // [nodes()] each (graph node ids), summed over the last run's requests
   void nodeImpact(uint32_t* lost, uint32_t* moved) const;
+  // gain mode: impact mode with the two-sided records of orh_whatif_gain
+  // (nearer and widened nodes, gain next to stretch), for batches with or
+  // without lowers; queued at the same points, same arguments. One mode per
+  // run: with setImpact on as well run() throws std::invalid_argument
+  void setGain(bool on, const std::vector<std::pair<std::string, uint32_t>>& weights = {},
+               bool nodeCounts = false);
+  // [requests()] records of the last run, in the caller's request order
+  void gain(orh_whatif_gain_rec* out) const;
+  // [nodes()] each (graph node ids), summed over the last run's requests
+  void nodeGain(uint32_t* lost, uint32_t* moved, uint32_t* nearer) const;
   // rows of request i; only the last chunk's rows are still in the buffers
   // (std::out_of_range otherwise)
   void fetch(size_t i, uint32_t* dist, uint32_t* nh) const;
@@ -140,20 +150,27 @@ class WhatIfBatch {
   uint32_t* dInfo_{nullptr};
   uint64_t* dDigest_{nullptr};      // [requests] (verification mode)
   uint64_t* dBaseDigest_{nullptr};  // [sources]
-  // impact mode
-  void queueImpact(size_t c);
+  // impact and gain mode (they share the weights and the node counters)
+  void queueImpact(size_t c);  // chunk c's summary in the mode that is on
   void freeImpact();
+  void setSummary(bool* mode, bool other, bool on, const std::vector<std::pair<std::string, uint32_t>>& weights,
+                  bool nodeCounts);
   bool impact_{false};
+  bool gain_{false};
   bool nodeCounts_{false};
   bool impactRan_{false};  // the last run filled dImpact_ (and the node arrays)
+  bool gainRan_{false};    // the last run filled dGain_ (and the node arrays)
   std::vector<uint32_t> weights_;            // [n_] (empty: none)
   orh_whatif_impact_rec* dImpact_{nullptr};  // [requests]
   uint32_t* dWeight_{nullptr};               // [n_]
   uint32_t* dNodeLost_{nullptr};             // [n_]
   uint32_t* dNodeMoved_{nullptr};            // [n_]
+  orh_whatif_gain_rec* dGain_{nullptr};      // [requests] (gain mode)
+  uint32_t* dNodeNearer_{nullptr};           // [n_] (gain mode)
   // the last run's results, kept on the host when release() frees the above
   std::vector<orh_whatif_impact_rec> hImpact_;
-  std::vector<uint32_t> hNodeLost_, hNodeMoved_;
+  std::vector<orh_whatif_gain_rec> hGain_;
+  std::vector<uint32_t> hNodeLost_, hNodeMoved_, hNodeNearer_;
 };
 
 }  // namespace openr_amd

@@ -1,6 +1,7 @@
 // Internal interface of the what-if repair kernels (whatif_kernels.hip), the
-// metric-lower pass behind them (whatif_lower_kernels.hip) and the impact
-// summaries over their rows (whatif_impact_kernels.hip).
+// metric-lower pass behind them (whatif_lower_kernels.hip), the impact
+// summaries over their rows (whatif_impact_kernels.hip) and the two-sided
+// summaries (whatif_gain_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +9,7 @@
 #include <stdint.h>
 
 struct orh_whatif_impact_rec;  // include/openr_hip.h
+struct orh_whatif_gain_rec;
 
 namespace orh {
 
@@ -156,5 +158,28 @@ struct ImpactArgs {
 };
 // zeroes the records, scans, then finishes max_stretch / worst_node
 hipError_t launch_whatif_impact(const ImpactArgs& a, hipStream_t s);
+
+// ---- two-sided what-if summaries (whatif_gain_kernels.hip) ----------------
+// the same comparison with the nodes that got nearer and those whose first-hop
+// set grew counted too (orh_whatif_gain in include/openr_hip.h has the classes)
+struct GainArgs {
+  uint32_t n_nodes;
+  uint32_t n_req;
+  const uint32_t* base_dist;  // [m][N]
+  const uint32_t* base_nh;    // [m][N], one mask word
+  const uint32_t* base_row;   // [n_req] base row of the request's source
+  const uint32_t* srcs;       // [n_req] its source node (in no class)
+  const uint32_t* dist;       // [n_req][N]
+  const uint32_t* nh;         // [n_req][N]
+  const uint32_t* info;       // [n_req] (nullable: every row is scanned); tier 0: the row is not read
+  const uint32_t* weight;     // [N] (nullable)
+  uint32_t* node_lost;        // [N] (nullable), accumulated
+  uint32_t* node_moved;       // [N] (nullable), accumulated
+  uint32_t* node_nearer;      // [N] (nullable), accumulated
+  ::orh_whatif_gain_rec* out;  // [n_req]
+};
+// zeroes the records, scans, then finishes max_stretch / worst_node and
+// max_gain / best_node
+hipError_t launch_whatif_gain(const GainArgs& a, hipStream_t s);
 
 }  // namespace orh

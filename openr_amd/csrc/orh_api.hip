@@ -2283,24 +2283,32 @@ int whatif_flush(orh_whatif* job) {
   return ORH_OK;
 }
 
-// orh_whatif_impact: the requests' rows against their sources' base rows,
-// one record each, on the context stream behind the runs that wrote the rows
-int whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const uint32_t* d_dist,
-                  const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_impact_opts* opts,
-                  orh_whatif_impact_rec* d_out) {
+// What orh_whatif_impact and orh_whatif_gain share: validation, the joins of
+// the runs that wrote the rows, and the staged (base row | source node) words
+// of the requests. `what` names the entry point in error messages.
+struct SummaryStage {
+  const uint32_t* base_dist;
+  const uint32_t* base_nh;
+  const uint32_t* base_row;  // device [n_req]
+  const uint32_t* srcs;      // device [n_req]
+  const uint32_t* info;      // the caller's d_info, or null where tier 0 proves nothing
+};
+int whatif_summary_stage(orh_whatif* job, const char* what, uint32_t n_req, const uint32_t* src_idx,
+                         const uint32_t* d_dist, const uint32_t* d_nh, const uint32_t* d_info, SummaryStage* out) {
   orh_graph* g = job->g;
   orh_ctx* ctx = g->ctx;
+  const std::string name(what);
   const uint32_t N = g->n_nodes, m = static_cast<uint32_t>(job->srcs.size());
   for (uint32_t i = 0; i < n_req; ++i)
-    if (src_idx[i] >= m) return fail(ctx, ORH_E_INVALID, "orh_whatif_impact: source index out of range");
+    if (src_idx[i] >= m) return fail(ctx, ORH_E_INVALID, name + ": source index out of range");
   const bool share = (job->flags & ORH_WHATIF_SHARE_BASE) != 0;
   if (share && !d_info)
-    return fail(ctx, ORH_E_INVALID, "orh_whatif_impact: a SHARE_BASE job's tier-0 rows were never written, d_info is needed");
+    return fail(ctx, ORH_E_INVALID, name + ": a SHARE_BASE job's tier-0 rows were never written, d_info is needed");
   // a graph whose runs have no tier-3 slots leaves tier 0 in d_info for the
   // requests its full search re-derived: tier 0 does not prove there that the
   // row stands, so every row is scanned
   if (repair_slots_for(N, g->n_recs, n_req) == 0) {
-    if (share) return fail(ctx, ORH_E_UNSUPPORTED, "orh_whatif_impact: SHARE_BASE on a graph without repair slots");
+    if (share) return fail(ctx, ORH_E_UNSUPPORTED, name + ": SHARE_BASE on a graph without repair slots");
     d_info = nullptr;
   }
   // every pending run whose rows overlap the given ones joins the context stream
@@ -2315,16 +2323,43 @@ int whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, cons
   job->imp_cur = (job->imp_cur + 1) % kRunSlots;
   ORH_HIP(ctx, hipMemcpyAsync(st.d, st.h, words * 4, hipMemcpyHostToDevice, ctx->stream));
   ORH_HIP(ctx, hipEventRecord(st.ev, ctx->stream));
+  out->base_dist = job->d_base;
+  out->base_nh = job->d_base + static_cast<size_t>(m) * N;
+  out->base_row = st.d;
+  out->srcs = st.d + n_req;
+  out->info = d_info;
+  return ORH_OK;
+}
+
+// the public entry points' checks before anything is staged
+int whatif_summary_check(orh_whatif* job, const char* what, const uint32_t* h_src_idx, const uint32_t* d_dist,
+                         const uint32_t* d_nh, const void* d_out) {
+  orh_ctx* ctx = job->g->ctx;
+  if (!h_src_idx || !d_dist || !d_nh || !d_out) return fail(ctx, ORH_E_INVALID, std::string(what) + ": null argument");
+  if (job->gen != job->g->gen)
+    return fail(ctx, ORH_E_STATE, std::string(what) + ": the graph changed since the job was created");
+  return ORH_OK;
+}
+
+// orh_whatif_impact: the requests' rows against their sources' base rows,
+// one record each, on the context stream behind the runs that wrote the rows
+int whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const uint32_t* d_dist,
+                  const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_impact_opts* opts,
+                  orh_whatif_impact_rec* d_out) {
+  orh_ctx* ctx = job->g->ctx;
+  SummaryStage st{};
+  const int rc = whatif_summary_stage(job, "orh_whatif_impact", n_req, src_idx, d_dist, d_nh, d_info, &st);
+  if (rc) return rc;
   orh::ImpactArgs a{};
-  a.n_nodes = N;
+  a.n_nodes = job->g->n_nodes;
   a.n_req = n_req;
-  a.base_dist = job->d_base;
-  a.base_nh = job->d_base + static_cast<size_t>(m) * N;
-  a.base_row = st.d;
-  a.srcs = st.d + n_req;
+  a.base_dist = st.base_dist;
+  a.base_nh = st.base_nh;
+  a.base_row = st.base_row;
+  a.srcs = st.srcs;
   a.dist = d_dist;
   a.nh = d_nh;
-  a.info = d_info;
+  a.info = st.info;
   if (opts) {
     a.weight = opts->d_weight;
     a.node_lost = opts->d_node_lost;
@@ -2333,6 +2368,36 @@ int whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, cons
   a.out = d_out;
   const hipError_t e = orh::launch_whatif_impact(a, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "what-if impact launch");
+  return ORH_OK;
+}
+
+// orh_whatif_gain: the same with the two-sided classes
+int whatif_gain(orh_whatif* job, uint32_t n_req, const uint32_t* src_idx, const uint32_t* d_dist,
+                const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_gain_opts* opts,
+                orh_whatif_gain_rec* d_out) {
+  orh_ctx* ctx = job->g->ctx;
+  SummaryStage st{};
+  const int rc = whatif_summary_stage(job, "orh_whatif_gain", n_req, src_idx, d_dist, d_nh, d_info, &st);
+  if (rc) return rc;
+  orh::GainArgs a{};
+  a.n_nodes = job->g->n_nodes;
+  a.n_req = n_req;
+  a.base_dist = st.base_dist;
+  a.base_nh = st.base_nh;
+  a.base_row = st.base_row;
+  a.srcs = st.srcs;
+  a.dist = d_dist;
+  a.nh = d_nh;
+  a.info = st.info;
+  if (opts) {
+    a.weight = opts->d_weight;
+    a.node_lost = opts->d_node_lost;
+    a.node_moved = opts->d_node_moved;
+    a.node_nearer = opts->d_node_nearer;
+  }
+  a.out = d_out;
+  const hipError_t e = orh::launch_whatif_gain(a, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "what-if gain launch");
   return ORH_OK;
 }
 
@@ -2537,11 +2602,23 @@ int orh_whatif_impact(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx
   orh_ctx* ctx = job->g->ctx;
   join_deferred(ctx);
   if (n_req == 0) return ORH_OK;
-  if (!h_src_idx || !d_dist || !d_nh || !d_out) return fail(ctx, ORH_E_INVALID, "orh_whatif_impact: null argument");
-  if (job->gen != job->g->gen)
-    return fail(ctx, ORH_E_STATE, "orh_whatif_impact: the graph changed since the job was created");
+  const int rc = whatif_summary_check(job, "orh_whatif_impact", h_src_idx, d_dist, d_nh, d_out);
+  if (rc) return rc;
   hipSetDevice(ctx->device);
   return whatif_impact(job, n_req, h_src_idx, d_dist, d_nh, d_info, opts, d_out);
+}
+
+int orh_whatif_gain(orh_whatif* job, uint32_t n_req, const uint32_t* h_src_idx, const uint32_t* d_dist,
+                    const uint32_t* d_nh, const uint32_t* d_info, const orh_whatif_gain_opts* opts,
+                    orh_whatif_gain_rec* d_out) {
+  if (!job) return ORH_E_INVALID;
+  orh_ctx* ctx = job->g->ctx;
+  join_deferred(ctx);
+  if (n_req == 0) return ORH_OK;
+  const int rc = whatif_summary_check(job, "orh_whatif_gain", h_src_idx, d_dist, d_nh, d_out);
+  if (rc) return rc;
+  hipSetDevice(ctx->device);
+  return whatif_gain(job, n_req, h_src_idx, d_dist, d_nh, d_info, opts, d_out);
 }
 
 int orh_whatif_refresh(orh_whatif* job) {
