@@ -24,7 +24,8 @@ EXT = sysconfig.get_config_var("EXT_SUFFIX")
 HOST_MOD = os.path.join(PKG, "_openr_host" + EXT)
 ARCH = os.environ.get("OPENR_HIP_ARCH", "gfx950")
 
-HIP_SRCS = [os.path.join(CSRC, "orh_api.hip")] + [
+HIP_SRCS = [os.path.join(CSRC, "orh_api.hip")] + [os.path.join(CSRC, "api", f + ".hip")
+                                                  for f in ("spf", "whatif", "ksp", "routes")] + [
     os.path.join(CSRC, "kernels", f + ".hip")
     for f in ("spf_msbfs_kernels", "spf_lds_kernels", "spf_wms_kernels", "spf_bfs_kernels",
               "spf_hop_kernels", "spf_hbm_kernels", "spf_dist_kernels", "spf_exact_kernels", "spf_plan",

@@ -10,7 +10,7 @@ the tests and by their child processes (one per process-wide switch).
 """
 from openr_amd.types import Adjacency, BinaryAddress, create_adj_db
 
-# orh_api.hip (orh_ksp2_batch) and ksp_kernels.hip
+# api/ksp.hip (orh_ksp2_batch) and ksp_kernels.hip
 OUT_CAP, IGN_CAP = 1024, 512
 WAVE_STACK, WAVE_HASH = 512, 1024
 THREAD_STACK, THREAD_HASH = 1024, 2048

@@ -37,6 +37,16 @@ def test_every_declared_symbol_is_exported(lib):
     assert not missing, f"symbols declared in openr_hip.h but not exported: {missing}"
 
 
+def test_exported_c_symbols_are_exactly_the_declared_ones(lib):
+    """The unmangled orh_* names of the dynamic symbol table equal the header's:
+    no helper of csrc/api/ leaks out as a C symbol, no unit is missing."""
+    import subprocess
+    from openr_amd import HIP_LIB_PATH
+    out = subprocess.run(["nm", "-D", "--defined-only", HIP_LIB_PATH], capture_output=True, text=True, check=True)
+    exported = sorted({f[-1] for f in (ln.split() for ln in out.stdout.splitlines()) if f and f[-1].startswith("orh_")})
+    assert exported == declared_symbols()
+
+
 def test_null_arguments_are_rejected_without_a_device(lib):
     lib.orh_create.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     assert lib.orh_create(0, 0, None) == -1  # ORH_E_INVALID

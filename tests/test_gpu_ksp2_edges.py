@@ -5,7 +5,7 @@ oracle's getKthPaths (LinkState.cpp:762-791) on the same adjacency databases
 loaded in the same order, link by link and in order; ksp_stats() equals the
 (device, host) split derived from the caps in the code.
 
-The caps (orh_api.hip orh_ksp2_batch, ksp_kernels.hip):
+The caps (api/ksp.hip orh_ksp2_batch, ksp_kernels.hip):
 
   per pair        wave kernel (default)    thread kernel (ORH_KSP_WAVE=0)
   DFS frames      kWaveStack = 512         kKspStackCap = 1024
