@@ -2,7 +2,8 @@
 ORH_WHATIF_T3_SPLIT=0 (the slot tier on the side stream), ORH_WHATIF_FULL=n
 (full searches for the head of the slot tier's queue, tier 2 skipped in front
 of them), ORH_WHATIF_SKIP_T2=0 (tier 2 kept), and a run with metric raises
-under ORH_WHATIF_FULL, which takes no full search.
+under ORH_WHATIF_FULL, which takes no full search. ORH_REPAIR_CAPS (the tiers'
+caps, the two-tier plan, full searches behind it) has test_gpu_whatif_caps.py.
 
 The switches are read once per process, so every setting runs in a child
 process of its own. The job is test_drain_tiers' (test_gpu_whatif_drain.py):

@@ -12,7 +12,10 @@ links that are not on any shortest path (the row is the base row), an
 affected set larger than the workgroup's LDS (the flagged full-search
 fallback), the existing ignore-set tests re-run with the repair forced on,
 and the 50k-node WAN (every row against the non-repair device path, sampled
-rows against the oracle).
+rows against the oracle). Requests with exactly cap and cap + 1 nodes or
+edges at every hand-off between the tiers, the two-tier plan, workgroups that
+take several requests, and the copy kernel beyond one tile are in
+test_gpu_whatif_caps.py.
 """
 import random
 
